@@ -18,10 +18,10 @@ for step in "$@"; do
     tests) run pytest_gpu 900 python -u -m pytest tests -m gpu -x -v --timeout 120 --timeout-method thread ;;
     testsall) run pytest_gpu 1100 python -u -m pytest tests -m gpu -v --timeout 120 --timeout-method thread ;;
     smoke) run smoke 300 python -c "import __graft_entry__ as g; g.smoke()" ;;
-    bench) run bench 900 python bench.py ;;
-    benchq) run bench 300 python bench.py --steps 10 --warmup 2 --no-cpu-baseline ;;
-    rehearse2) run bench_rehearse2 900 env PG_BENCH_REHEARSE=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 2 --steps 2 --warmup 1 ;;
-    rehearse2c3) run bench_rehearse2c3 600 env PG_BENCH_REHEARSE=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29612 bench.py --gpus 2 --config c3 --steps 3 --warmup 1 ;;
+    bench) run bench 900 python bench.py --full ;;
+    benchq) run bench 300 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline ;;
+    rehearse2) run bench_rehearse2 900 env PG_BENCH_REHEARSE=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29611 bench.py --gpus 2 --full --steps 2 --warmup 1 ;;
+    rehearse2c3) run bench_rehearse2c3 600 env PG_BENCH_REHEARSE=1 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29612 bench.py --gpus 2 --full --config c3 --steps 3 --warmup 1 ;;
     cover) run pytest_cover 600 python -u -m pytest tests/test_gpu_parity.py tests/test_gpu_parse.py tests/test_gpu_rccl.py -k "k3 or early_split or build_host or rccl or last_chunk" -v --timeout 120 --timeout-method thread ;;
     dbgc3) run dbg_c3 400 env PG_LIB_NAME=libpangenome_hip_dbg.so python -u tools/dbg_host_c3.py 0 2 ;;
     missing) run dbg_missing 400 env PG_LIB_NAME=libpangenome_hip_dbg.so python -u tools/dbg_missing.py gpurun_out/missing.npz ;;
@@ -29,9 +29,9 @@ for step in "$@"; do
     bracketcat) run bracket_cat 900 python -u tools/corruption_bracket.py cat ;;
     bracket) run bracket_sort 500 python -u tools/corruption_bracket.py sort ;;
     abc4dbg) run ab_c4dbg 600 env PG_DEBUG_BUILD=1 python -u tools/ab_k3.py --genomes 1000 --steps 2 --tune base ;;
-    benchc4) run bench_c4 900 python bench.py --config c4 --steps 5 --warmup 2 --no-cpu-baseline --no-cli ;;
-    benchsmall) run bench_small 600 python bench.py --config small --steps 5 --warmup 1 --no-cpu-baseline ;;
-    benchc2) run bench_c2 600 python bench.py --config c2 --steps 20 --warmup 3 --no-cpu-baseline ;;
+    benchc4) run bench_c4 900 python bench.py --full --config c4 --steps 5 --warmup 2 --no-cpu-baseline --no-cli ;;
+    benchsmall) run bench_small 600 python bench.py --full --config small --steps 5 --warmup 1 --no-cpu-baseline ;;
+    benchc2) run bench_c2 600 python bench.py --full --config c2 --steps 20 --warmup 3 --no-cpu-baseline ;;
     prof) run prof 900 rocprofv3 --kernel-trace --stats -d gpurun_out/prof -o run --output-format csv -- python bench.py --steps 5 --warmup 1 --no-cpu-baseline --no-host-window --no-cli --no-exchange --no-concurrent --no-c5 ;;
     pmcsq) bash tools/pmc_kernels.sh "k_emit_work|k_cover_p|k_build_range|k_emit\(|k_span_sum|k_split" sq ;;
     pmc) bash tools/pmc_kernels.sh "k_span_sum|k_emit|k_records|k_pack_fix|k_cover|k_short_emit|k_split|k_build_range|rocprim" tr traffic ;;
@@ -59,9 +59,9 @@ for step in "$@"; do
     newtests) run pytest_new 600 python -u -m pytest tests/test_gpu_parity.py -k "empty or device_resident" -x -v --timeout 120 --timeout-method thread ;;
     k1) run pytest_k1 600 python -u -m pytest tests/test_gpu_parse.py -k "-8] or -24] or -40] or one_read" -x -v --timeout 300 --timeout-method thread && run ab_k1 600 python -u tools/ab_k3.py --alt --steps 16 --tune base --tune K1=8 --tune K1=24 --tune K1=40 --tune K1=72 ;;
     k1prof) run k1_prof 600 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_k1 -o run --output-format csv -- python -u tools/ab_k3.py --alt --steps 6 --tune base --tune K1=8 --tune K1=24 ;;
-    benchfull) run bench_full 900 python bench.py --gpus 1 --steps 20 --warmup 5 ;;
+    benchfull) run bench_full 900 python bench.py --gpus 1 --full --steps 20 --warmup 5 ;;
     c5pmc) for c in "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAVES" "SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_LDS_IDX_ACTIVE"; do i=$((${i:-0}+1)); run c5pmc_$i 300 timeout -s KILL 280 rocprofv3 --pmc $c --kernel-include-regex "k_cover_p|k_emit_work|k_route_scatter|k_route_emit|k_split|k_build_range|k_span_sum|k_emit" -d gpurun_out/c5pmc_$i -o pmc --output-format csv -- python -u tools/c5_probe.py stream routed reps=2; done ;;
-    benchc5q) run bench_c5q 600 python bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-cli --no-concurrent ;;
+    benchc5q) run bench_c5q 600 python bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-cli --no-concurrent ;;
     *) echo "unknown step $step"; exit 2 ;;
   esac
 done

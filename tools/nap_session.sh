@@ -4,7 +4,7 @@
 set -o pipefail
 o=gpurun_out/nap2; mkdir -p $o
 for L in "$@"; do
-  PG_LIB_NAME=libpangenome_hip$L.so timeout -k 10 200 python bench.py --steps 30 --warmup 5 --no-concurrent > $o/bench$L.json 2> $o/bench$L.err || exit 3
+  PG_LIB_NAME=libpangenome_hip$L.so timeout -k 10 200 python bench.py --full --steps 30 --warmup 5 --no-concurrent > $o/bench$L.json 2> $o/bench$L.err || exit 3
   python - "$o/bench$L.json" "$L" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])
