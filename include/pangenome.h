@@ -272,6 +272,41 @@ int pg_labels_from_edges(pg_ctx* ctx, const uint64_t* tuples, uint64_t n_edges, 
  * by label (cap >= n_labels). */
 int pg_labels_export(pg_ctx* ctx, int64_t* key, int64_t* value, int64_t* label, uint64_t cap);
 
+/* ---- built-in clustering of the `.xyz` graph (reference README step 4:
+ *      "remove weak edges in rdBG and index the connect components"), for runs
+ *      without the external `mcl` program.  Added after round 6 together with
+ *      pg_clusters_format and pg_clusters_format_fd.
+ * Input: the edges as the .xyz lists them (n_edges x 4 uint64 tuples and their
+ * int64 counts), or tuples == NULL for the last pg_edges in first-occurrence
+ * order (counts and n_edges are then ignored), and min_weight >= 1.
+ * Nodes: every distinct (key, value) among (n0, v0) and (n1, v1); the same key
+ * with two values is two nodes.  A node's id is its rank of first appearance,
+ * reading n0_v0 then n1_v1 of each edge in list order (pg_labels_from_edges'
+ * order).  Values fit 32 bits; 2^32 nodes or more is PG_ERANGE.
+ * Components: two nodes are joined iff a path of edges with count >=
+ * min_weight connects them.  Lighter edges and self-loops join nothing, but
+ * their endpoints are nodes: a node without a surviving edge is a cluster of 1.
+ * Order: clusters by size descending (mcl's convention), ties by the smallest
+ * node id ascending; the position of a cluster is its label.  Members inside a
+ * cluster by node id ascending.  The result depends on the input alone.
+ * Text (`.mcl` format): one line per cluster, members "<key>_<value>" as
+ * unsigned decimals (as pg_edges_format writes them) separated by '\t', the
+ * line ended by '\n'; no edges give an empty text.
+ * Label table: replaced, as by pg_labels_from_edges, with (key, value) ->
+ * line index for every node in file order (pg_labels_export returns that
+ * order): the table the written file gives through the `.mcl` reuse path.
+ * *n_clusters, *n_nodes (each may be NULL): lines and tokens of the text.
+ * PG_EINVAL (before any device work): NULL ctx, min_weight < 1, tuples without
+ * counts, a node value above 2^32 - 1. */
+int pg_cluster_cc(pg_ctx* ctx, const uint64_t* tuples, const int64_t* counts, uint64_t n_edges, int64_t min_weight,
+                  uint64_t* n_clusters, uint64_t* n_nodes);
+/* The `.mcl` text of the last pg_cluster_cc (kept on the device).  out ==
+ * NULL: only *n_bytes (the size) is set; otherwise cap >= that size, else
+ * PG_ERANGE.  PG_EINVAL before any pg_cluster_cc. */
+int pg_clusters_format(pg_ctx* ctx, char* out, uint64_t cap, uint64_t* n_bytes);
+/* The same text written to descriptor fd, as pg_edges_format_fd writes. */
+int pg_clusters_format_fd(pg_ctx* ctx, int fd, uint64_t* n_bytes);
+
 /* ---- region rows: seqs2path_jit_ (kmer_numba.py:1830-1849) -> seq2path_jit_
  *      (:1523-1573).  Labels are the host-built label_dct (:1918-1944):
  *      (key, value) -> label. */

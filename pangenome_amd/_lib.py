@@ -94,6 +94,9 @@ SIGNATURES = {
     "pg_edges_format_fd": (C.c_int, [_P, C.c_int, _U64P]),
     "pg_labels_from_edges": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, C.c_int64, _U64P]),
     "pg_labels_export": (C.c_int, [_P, _P, _P, _P, C.c_uint64]),
+    "pg_cluster_cc": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int64, _U64P, _U64P]),
+    "pg_clusters_format": (C.c_int, [_P, _P, C.c_uint64, _U64P]),
+    "pg_clusters_format_fd": (C.c_int, [_P, C.c_int, _U64P]),
     "pg_rows_format": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint64, _U64P]),
     "pg_rows_format_fd": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, _U64P]),
     "pg_get_stats": (C.c_int, [_P, _SP]),
@@ -487,10 +490,42 @@ class Context:
         self.label_gen = getattr(self, "label_gen", 0) + 1
         return n.value
 
+    def cluster_cc(self, tuples=None, counts=None, min_weight: int = 1):
+        """The built-in clusterer (pg_cluster_cc): edges with count <
+        min_weight dropped, the connected components of the rest as clusters
+        (size descending, then first appearance).  tuples None: the last
+        edges() pass on the device.  Replaces the label table with (key,
+        value) -> `.mcl` line index; returns (n_clusters, n_nodes)."""
+        nc, nu = C.c_uint64(), C.c_uint64()
+        t = None if tuples is None else np.ascontiguousarray(tuples, dtype=np.uint64).reshape(-1, 4)
+        cn = None if counts is None else np.ascontiguousarray(counts, dtype=np.int64)
+        if t is not None and cn is not None and cn.shape[0] != t.shape[0]:
+            raise ValueError("cluster_cc: %d tuples, %d counts" % (t.shape[0], cn.shape[0]))
+        check(self.lib.pg_cluster_cc(self.h, ptr(t), ptr(cn), 0 if t is None else t.shape[0], int(min_weight),
+                                     C.byref(nc), C.byref(nu)), "pg_cluster_cc")
+        self.n_labels = nu.value
+        self.label_gen = getattr(self, "label_gen", 0) + 1
+        return nc.value, nu.value
+
+    def clusters_text(self) -> bytes:
+        """The `.mcl` text of the last cluster_cc (pg_clusters_format)."""
+        n = C.c_uint64()
+        check(self.lib.pg_clusters_format(self.h, None, 0, C.byref(n)), "pg_clusters_format")
+        buf = np.empty(max(n.value, 1), np.uint8)
+        check(self.lib.pg_clusters_format(self.h, ptr(buf), buf.shape[0], C.byref(n)), "pg_clusters_format")
+        return buf[:n.value].tobytes()
+
+    def clusters_write(self, fd: int) -> int:
+        """clusters_text() written straight to descriptor fd at its position
+        (pg_clusters_format_fd); flush any buffered writer on fd first."""
+        n = C.c_uint64()
+        check(self.lib.pg_clusters_format_fd(self.h, int(fd), C.byref(n)), "pg_clusters_format_fd")
+        return n.value
+
     def labels(self, gen=None):
         """(keys, vals, ids) of the device label table, in insertion order.
         `gen`: the label_gen a caller's view was made at; a later label pass
-        (set_labels / labels_from_edges) on this context replaced that table,
+        (set_labels / labels_from_edges / cluster_cc) on this context replaced that table,
         and reading it then raises instead of returning the newer labels."""
         if gen is not None and gen != getattr(self, "label_gen", 0):
             raise RuntimeError("label table: replaced by a later label pass on this context (generation %d, now %d)"

@@ -94,7 +94,7 @@ void pg_destroy(pg_ctx* x) {
                         &c.recS_mw[1], &c.ctrS, &c.snapA, &c.rseg, &c.k5_ctr, &c.tile_sched, &c.tile_desc, &c.k3_queue,
                         &c.k3_hint, &c.part_cnt, &c.tile_cnt, &c.tile_off, &c.occ, &c.edge_tab, &c.pair_tab,
                         &c.edge_out, &c.edge_exp, &c.lab_tab, &c.lab_list, &c.rows_buf, &c.text_len, &c.text_off,
-                        &c.text_buf, &c.text_names, &c.preload,
+                        &c.text_buf, &c.text_names, &c.clu_text, &c.preload,
                         &c.dump_cnt};
   for (auto* b : bufs) b->release();
   pg::pool_destroy(c);
@@ -668,6 +668,39 @@ int pg_labels_export(pg_ctx* x, int64_t* key, int64_t* value, int64_t* label, ui
     if (!x || !key || !value || !label) throw pg::Error(PG_EINVAL, "pg_labels_export: bad arguments");
     PG_HIP(hipSetDevice(x->c.device));
     pg::export_labels(x->c, key, value, label, cap);
+  });
+}
+
+int pg_cluster_cc(pg_ctx* x, const uint64_t* tuples, const int64_t* counts, uint64_t n_edges, int64_t min_weight,
+                  uint64_t* n_clusters, uint64_t* n_nodes) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_cluster_cc: ctx is NULL");
+    if (min_weight < 1) throw pg::Error(PG_EINVAL, "pg_cluster_cc: min_weight below 1");
+    if (tuples && !counts) throw pg::Error(PG_EINVAL, "pg_cluster_cc: tuples without counts");
+    if (!tuples && counts) throw pg::Error(PG_EINVAL, "pg_cluster_cc: counts without tuples");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::cluster_cc(x->c, tuples, counts, n_edges, min_weight);
+    if (n_clusters) *n_clusters = x->c.n_clusters;
+    if (n_nodes) *n_nodes = x->c.n_clu_nodes;
+  });
+}
+
+int pg_clusters_format(pg_ctx* x, char* out, uint64_t cap, uint64_t* n_bytes) {
+  return guard([&] {
+    if (!x || !n_bytes) throw pg::Error(PG_EINVAL, "pg_clusters_format: bad arguments");
+    if (!x->c.clu_ready) throw pg::Error(PG_EINVAL, "pg_clusters_format: no clustering (call pg_cluster_cc first)");
+    if (out && cap < x->c.clu_total) throw pg::Error(PG_ERANGE, "pg_clusters_format: buffer too small");
+    PG_HIP(hipSetDevice(x->c.device));
+    *n_bytes = pg::format_clusters(x->c, out, cap);
+  });
+}
+
+int pg_clusters_format_fd(pg_ctx* x, int fd, uint64_t* n_bytes) {
+  return guard([&] {
+    if (!x || !n_bytes || fd < 0) throw pg::Error(PG_EINVAL, "pg_clusters_format_fd: bad arguments");
+    if (!x->c.clu_ready) throw pg::Error(PG_EINVAL, "pg_clusters_format_fd: no clustering (call pg_cluster_cc first)");
+    PG_HIP(hipSetDevice(x->c.device));
+    *n_bytes = pg::format_clusters(x->c, nullptr, 0, fd);
   });
 }
 

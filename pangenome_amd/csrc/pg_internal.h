@@ -286,6 +286,10 @@ struct Ctx {
   DevBuf text_len, text_off, text_buf, text_names;
   uint64_t text_total = 0;
   bool text_xyz = false, text_rows = false;
+  // ---- built-in clustering (pg_cluster.hip): the `.mcl` text of the last pg_cluster_cc
+  DevBuf clu_text;
+  uint64_t clu_total = 0, n_clusters = 0, n_clu_nodes = 0;
+  bool clu_ready = false;
 
   // ---- npz persistence (pg_persist.hip)
   DevBuf preload;                 // staged PreEnt pairs, OR-merged by every build
@@ -399,8 +403,17 @@ uint64_t format_edges(Ctx& c, char* out, uint64_t cap, int fd = -1);
 uint64_t labels_from_edges(Ctx& c, const uint64_t* h_tuples, uint64_t n_edges, const int64_t* mk, const int64_t* mv,
                            const int64_t* mi, uint64_t n_mcl, int64_t next_id);
 void export_labels(Ctx& c, int64_t* key, int64_t* val, int64_t* id, uint64_t cap);
+// the label hash table of n (key, value, label) device entries (c.lab_tab), on c.stream
+void lab_build(Ctx& c, const long long* d_key, const long long* d_val, const long long* d_id, uint64_t n);
 uint64_t format_rows_text(Ctx& c, const char* names, const int64_t* name_off, uint64_t n_names, char* out,
                           uint64_t cap, int fd = -1);
+
+// pg_cluster.hip
+// Weight cut + connected components of the `.xyz` graph; h_tuples NULL: the
+// last edge pass (c.edge_exp).  Replaces the label table; keeps the `.mcl`
+// text on the device for format_clusters.
+void cluster_cc(Ctx& c, const uint64_t* h_tuples, const int64_t* h_counts, uint64_t n_edges, int64_t min_weight);
+uint64_t format_clusters(Ctx& c, char* out, uint64_t cap, int fd = -1);
 
 // helpers
 inline uint64_t next_pow2(uint64_t x) {

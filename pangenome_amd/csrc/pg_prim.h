@@ -1,0 +1,75 @@
+// pg_prim.h — rocPRIM calls on the context's stream and scratch, and the
+// decimal text helpers, shared by the walk passes (pg_walk.hip) and the
+// clusterer (pg_cluster.hip).
+#pragma once
+#include <rocprim/rocprim.hpp>
+
+#include "pg_internal.h"
+
+namespace pg {
+
+template <class F>
+static void with_temp(Ctx& c, F&& f) {
+  size_t bytes = 0;
+  PG_HIP(f((void*)nullptr, bytes));
+  c.scratch.reserve(bytes + 16);
+  bytes = c.scratch.cap;
+  PG_HIP(f(c.scratch.p, bytes));
+}
+
+template <class K, class V>
+static void sort_pairs(Ctx& c, const K* kin, K* kout, const V* vin, V* vout, uint64_t n, int end_bit) {
+  with_temp(c, [&](void* tmp, size_t& bytes) {
+    return rocprim::radix_sort_pairs(tmp, bytes, kin, kout, vin, vout, (size_t)n, 0, end_bit, c.stream);
+  });
+}
+template <class T>
+static uint64_t select_flagged(Ctx& c, const T* in, const uint8_t* flags, T* out, uint64_t n, DevBuf& cnt) {
+  cnt.reserve(16);
+  with_temp(c, [&](void* tmp, size_t& bytes) {
+    return rocprim::select(tmp, bytes, in, flags, out, cnt.as<unsigned long long>(), (size_t)n, c.stream);
+  });
+  unsigned long long h = 0;
+  PG_HIP(hipMemcpyAsync(&h, cnt.p, 8, hipMemcpyDeviceToHost, c.stream));
+  c.sync();
+  return h;
+}
+[[maybe_unused]] static uint64_t excl_scan_total(Ctx& c, const unsigned long long* len, unsigned long long* off,
+                                                 uint64_t n) {
+  // off[0..n]: exclusive prefix sums, off[n] = total
+  PG_HIP(hipMemsetAsync(const_cast<unsigned long long*>(len) + n, 0, 8, c.stream));
+  with_temp(c, [&](void* tmp, size_t& bytes) {
+    return rocprim::exclusive_scan(tmp, bytes, len, off, 0ull, (size_t)n + 1, rocprim::plus<unsigned long long>(),
+                                   c.stream);
+  });
+  unsigned long long h = 0;
+  PG_HIP(hipMemcpyAsync(&h, off + n, 8, hipMemcpyDeviceToHost, c.stream));
+  c.sync();
+  return h;
+}
+[[maybe_unused]] static int bits_for(uint64_t maxv) {
+  int b = 1;
+  while (b < 64 && (maxv >> b)) ++b;
+  return b;
+}
+
+// pg_walk.hip: the node slots of an edge list (n0, v0, n1, v1) as sort keys
+// with their positions, and dst[t] = src[pos[t]]
+__global__ void k_nodes(const unsigned long long* __restrict__ tup, uint64_t nn, unsigned long long* __restrict__ key,
+                        unsigned* __restrict__ val, unsigned long long* __restrict__ pos);
+__global__ void k_gather_key(const unsigned long long* __restrict__ src, const unsigned long long* __restrict__ pos,
+                             uint64_t n, unsigned long long* __restrict__ dst);
+
+// decimal digits of v (v >= 0)
+__host__ __device__ __forceinline__ uint32_t ndig(unsigned long long v) {
+  uint32_t d = 1;
+  while (v >= 10ull) { v /= 10ull; ++d; }
+  return d;
+}
+__device__ __forceinline__ char* put_dec(char* o, unsigned long long v) {
+  const uint32_t d = ndig(v);
+  for (uint32_t i = d; i-- > 0;) { o[i] = (char)('0' + v % 10ull); v /= 10ull; }
+  return o + d;
+}
+
+}  // namespace pg

@@ -15,6 +15,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "pg_internal.h"
+#include "pg_prim.h"
 
 namespace pg {
 
@@ -466,19 +467,8 @@ __global__ void k_rows(const Hit* __restrict__ hits, const unsigned long long* _
 }
 
 // ------------------------------------------------------------ text
-// decimal digits of v (v >= 0)
-__host__ __device__ __forceinline__ uint32_t ndig(unsigned long long v) {
-  uint32_t d = 1;
-  while (v >= 10ull) { v /= 10ull; ++d; }
-  return d;
-}
 __device__ __forceinline__ uint32_t ndig_i(long long v) {
   return v < 0 ? 1 + ndig((unsigned long long)0 - (unsigned long long)v) : ndig((unsigned long long)v);
-}
-__device__ __forceinline__ char* put_dec(char* o, unsigned long long v) {
-  const uint32_t d = ndig(v);
-  for (uint32_t i = d; i-- > 0;) { o[i] = (char)('0' + v % 10ull); v /= 10ull; }
-  return o + d;
 }
 __device__ __forceinline__ char* put_dec_i(char* o, long long v) {
   if (v < 0) { *o++ = '-'; return put_dec(o, (unsigned long long)0 - (unsigned long long)v); }
@@ -582,15 +572,6 @@ __global__ void k_iota64(unsigned long long* __restrict__ out, uint64_t n) {
 }
 
 // ------------------------------------------------------------------ host
-template <class F>
-static void with_temp(Ctx& c, F&& f) {
-  size_t bytes = 0;
-  PG_HIP(f((void*)nullptr, bytes));
-  c.scratch.reserve(bytes + 16);
-  bytes = c.scratch.cap;
-  PG_HIP(f(c.scratch.p, bytes));
-}
-
 struct WalkPlan {
   std::vector<int> recs;                   // walked records, in order
   std::vector<unsigned long long> run_off; // per walked record
@@ -692,42 +673,6 @@ static uint64_t walk_collect(Ctx& c, WalkPlan& P, WalkArgs& a, DevBuf& out, size
   PG_HIP(hipGetLastError());
   c.sync();
   return total;
-}
-
-// rocPRIM helpers on the context's stream and scratch
-template <class K, class V>
-static void sort_pairs(Ctx& c, const K* kin, K* kout, const V* vin, V* vout, uint64_t n, int end_bit) {
-  with_temp(c, [&](void* tmp, size_t& bytes) {
-    return rocprim::radix_sort_pairs(tmp, bytes, kin, kout, vin, vout, (size_t)n, 0, end_bit, c.stream);
-  });
-}
-template <class T>
-static uint64_t select_flagged(Ctx& c, const T* in, const uint8_t* flags, T* out, uint64_t n, DevBuf& cnt) {
-  cnt.reserve(16);
-  with_temp(c, [&](void* tmp, size_t& bytes) {
-    return rocprim::select(tmp, bytes, in, flags, out, cnt.as<unsigned long long>(), (size_t)n, c.stream);
-  });
-  unsigned long long h = 0;
-  PG_HIP(hipMemcpyAsync(&h, cnt.p, 8, hipMemcpyDeviceToHost, c.stream));
-  c.sync();
-  return h;
-}
-static uint64_t excl_scan_total(Ctx& c, const unsigned long long* len, unsigned long long* off, uint64_t n) {
-  // off[0..n]: exclusive prefix sums, off[n] = total
-  PG_HIP(hipMemsetAsync(const_cast<unsigned long long*>(len) + n, 0, 8, c.stream));
-  with_temp(c, [&](void* tmp, size_t& bytes) {
-    return rocprim::exclusive_scan(tmp, bytes, len, off, 0ull, (size_t)n + 1, rocprim::plus<unsigned long long>(),
-                                   c.stream);
-  });
-  unsigned long long h = 0;
-  PG_HIP(hipMemcpyAsync(&h, off + n, 8, hipMemcpyDeviceToHost, c.stream));
-  c.sync();
-  return h;
-}
-static int bits_for(uint64_t maxv) {
-  int b = 1;
-  while (b < 64 && (maxv >> b)) ++b;
-  return b;
 }
 
 uint64_t walk_edges(Ctx& c, const uint8_t* h_rec_flag, int rc1) {
@@ -872,7 +817,7 @@ uint64_t format_edges(Ctx& c, char* out, uint64_t cap, int fd) {
   return c.text_total;
 }
 
-static void lab_build(Ctx& c, const long long* d_key, const long long* d_val, const long long* d_id, uint64_t n) {
+void lab_build(Ctx& c, const long long* d_key, const long long* d_val, const long long* d_id, uint64_t n) {
   const uint64_t cap = next_pow2(std::max<uint64_t>(1024, 2 * n + 16));
   c.lab_cap = cap;
   c.lab_tab.reserve(sizeof(LabSlot) * cap);

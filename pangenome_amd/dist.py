@@ -34,7 +34,7 @@ per-base work of every pass runs on each rank's own GPU over its own records:
              rank order — and reduces them by edge (walk counts add, the first
              occurrence wins), then applies the checkpoint reversals
              (host.edge_order / host.merge_edges for -R).
-6. labels    rank 0 writes `.xyz`, runs `mcl` (or reuses `.mcl`) and builds
+6. labels    rank 0 writes `.xyz`, runs `mcl` or the built-in clusterer (or reuses `.mcl`) and builds
              the label table (:1893-1944); it is broadcast to every rank.
 7. rows      every rank computes and formats its records' region rows
              (seqs2path_jit_ :1830-1849); rank 0 gathers the text in rank
@@ -1110,6 +1110,11 @@ class GpuShard:
     def edges(self, flags, rc1):
         return self.ctx.edges(flags, bool(rc1))
 
+    def cluster_cc(self, tuples, counts, min_weight):
+        """the `.mcl` bytes of the built-in clusterer over a host edge list"""
+        self.ctx.cluster_cc(tuples, counts, int(min_weight))
+        return self.ctx.clusters_text()
+
     def rows_text(self, labels, flags, rc1, names):
         self.ctx.set_labels(*labels)
         self.ctx.rows_count(flags, bool(rc1))
@@ -1315,8 +1320,10 @@ class DistRun:
         self.reduced = True
 
     # -------------------------------------------------------------- graph
-    def graph(self, Ns, rc1, brkpt="", cluster=True):
-        """seq2graph (:1853-1951) over the shards."""
+    def graph(self, Ns, rc1, brkpt="", cluster=True, min_weight=1):
+        """seq2graph (:1853-1951) over the shards.  cluster="cc": without a
+        `.mcl`, rank 0 writes one with the built-in clusterer (on its device,
+        or host.cluster_cc for a backend without one) instead of running mcl."""
         loaded, resume = None, None
         if brkpt and os.path.isfile(brkpt):
             offset, lt, lc = host.read_edge_npz(brkpt)
@@ -1351,6 +1358,14 @@ class DistRun:
             if cluster:
                 if os.path.isfile("%s.mcl" % oname):
                     self.say("# the mcl has been ran")
+                elif cluster == "cc":
+                    if hasattr(self.sh, "cluster_cc"):
+                        mcl_bytes = self.sh.cluster_cc(tuples, counts, int(min_weight))
+                    else:
+                        mcl_bytes = host.cluster_cc(tuples, counts, int(min_weight))[0].encode()
+                    with open(oname + ".mcl.tmp", "wb") as f:   # (renamed when whole: the file is reused if present)
+                        f.write(mcl_bytes)
+                    os.replace(oname + ".mcl.tmp", oname + ".mcl")
                 else:
                     self.out.flush()
                     os.system("mcl %s --abc -I 1.5 -te 8 -o %s.mcl -q x -V all" % (oname, oname))
@@ -1403,10 +1418,11 @@ def entry_point(argv, out=None, shard_factory=None, device=None, dev_index: int 
     args = parse_args(argv)
     qry, kmer, Ns = args["-i"], int(args["-k"]), host.eval_number(args["-n"])
     bkt, dbs, rbk, rc, rdb = args["-r"], args["-d"], args["-R"], int(args["-c"]), args["-D"]
-    if not qry:
+    if not qry or args["-a"] not in ("mcl", "cc"):
         if dist.get_rank() == 0:
             manual_print(out)
         raise SystemExit()
+    clu = dict(cluster="cc", min_weight=int(args["-w"])) if args["-a"] == "cc" else {}
     rc0, rc1 = (rc >> 1) == 1, (rc & 1) == 1
     k = min(max(1, kmer), 27)
     shard = shard_factory(k) if shard_factory else GpuShard(k, dev_index)
@@ -1422,7 +1438,7 @@ def entry_point(argv, out=None, shard_factory=None, device=None, dev_index: int 
         else:
             run.load_dbg(rdb, True, rc0)
         run.say("# find fr")
-        run.graph(Ns, rc1, brkpt=rbk)
+        run.graph(Ns, rc1, brkpt=rbk, **clu)
         return 0
     run.say("# build the dBG")
     st = time()
@@ -1441,7 +1457,7 @@ def entry_point(argv, out=None, shard_factory=None, device=None, dev_index: int 
     run.say("# finished in", time() - st, "seconds")
     run.say("# find fr")
     st = time()
-    run.graph(Ns, rc1, brkpt=rbk)
+    run.graph(Ns, rc1, brkpt=rbk, **clu)
     run.say("# finished in", time() - st, "seconds")
     return 0
 

@@ -257,6 +257,63 @@ def mcl_labels(mcl_text: str):
     return mk, mv, mi, flag
 
 
+def cluster_cc(tuples: np.ndarray, counts: np.ndarray, min_weight: int = 1):
+    """The built-in clusterer's specification (pg_cluster_cc computes the same
+    on the device): the `.xyz` edges with count < min_weight dropped, the
+    connected components of the rest (reference README step 4).  Nodes are the
+    distinct (key, value) pairs, numbered by first appearance (n0_v0, then
+    n1_v1 of each edge, in edge order); light edges and self-loops join
+    nothing, but their endpoints are nodes.  Clusters by size descending, ties
+    by their smallest node id; members by node id.  Returns the `.mcl` text
+    (one line per cluster, "<key>_<value>" tokens separated by tabs) and the
+    label table (keys, vals, ids) in file order, ids = line indices: what
+    mcl_labels(text) gives."""
+    if int(min_weight) < 1:
+        raise ValueError("cluster_cc: min_weight below 1")
+    t = np.ascontiguousarray(tuples, dtype=np.uint64).reshape(-1, 4)
+    cnt = np.ascontiguousarray(counts, dtype=np.int64)
+    if cnt.shape[0] != t.shape[0]:
+        raise ValueError("cluster_cc: %d tuples, %d counts" % (t.shape[0], cnt.shape[0]))
+    nodes = np.ascontiguousarray(t.reshape(-1, 2))           # slot 2e is (n0, v0), slot 2e + 1 is (n1, v1)
+    if nodes.shape[0] == 0:
+        z = np.zeros(0, np.int64)
+        return "", z, z.copy(), z.copy()
+    vv = nodes.view(np.dtype((np.void, 16))).ravel()
+    _, first, inv = np.unique(vv, return_index=True, return_inverse=True)
+    order = np.argsort(first, kind="stable")                 # groups by first appearance
+    rank = np.empty(order.shape[0], np.int64)
+    rank[order] = np.arange(order.shape[0])
+    ids = rank[inv.ravel()].reshape(-1, 2)                   # node ids of each edge's ends
+    uniq = nodes[first[order]]
+    U = uniq.shape[0]
+    parent = list(range(U))
+    keep = cnt >= int(min_weight)
+    for a, b in ids[keep].tolist():
+        while parent[a] != a:                                # find with path halving
+            parent[a] = parent[parent[a]]
+            a = parent[a]
+        while parent[b] != b:
+            parent[b] = parent[parent[b]]
+            b = parent[b]
+        if a != b:                                           # the larger root under the smaller
+            if a < b:
+                a, b = b, a
+            parent[a] = b
+    members = {}
+    for i in range(U):                                       # roots are their component's smallest id
+        r = i
+        while parent[r] != r:
+            r = parent[r]
+        parent[i] = r
+        members.setdefault(r, []).append(i)
+    clusters = sorted(members.items(), key=lambda kv: (-len(kv[1]), kv[0]))
+    names = ["%d_%d" % (a, b) for a, b in uniq.tolist()]
+    text = "".join("\t".join(names[i] for i in m) + "\n" for _, m in clusters)
+    file_order = np.fromiter((i for _, m in clusters for i in m), dtype=np.int64, count=U)
+    line = np.repeat(np.arange(len(clusters), dtype=np.int64), [len(m) for _, m in clusters])
+    return text, uniq[file_order, 0].view(np.int64), uniq[file_order, 1].view(np.int64), line
+
+
 def label_table(mcl_text: str, tuples: np.ndarray):
     """label_dict + label_arrays without the text round trip: the `.mcl` line
     index of every token (a later line wins, as dict assignment does), then

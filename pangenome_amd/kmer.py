@@ -9,7 +9,7 @@ runs in libpangenome_hip.so on an MI355X (pangenome_amd/csrc).  Mirrors:
   dbg2rdbg     :1313-1321                rdBG (K5 degree scan + compaction)
   seq2graph    :1853-1951                edges -> .xyz -> mcl -> labels -> rows
   dump / load_on_disk  :243-335         `<in>_db.npz` (oakht slot layout)
-  entry_point  :1971-2146                CLI (-i -k -n -c -r -d -R -D)
+  entry_point  :1971-2146                CLI (-i -k -n -c -r -d -R -D; ours: -a -w)
 
 Usage:  python -m pangenome_amd -i genomes.fa -k 27 > result.tab
 """
@@ -248,11 +248,14 @@ def rdbg_edges(g: DeviceGraph, Ns, chunk, rc, brkpt="", keep_on_device=False):
 
 
 def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_dict=None, saved=None,
-              hashfunc=None, jit=True, chunk=2 ** 33, rc=False, cluster=True, out=None):
+              hashfunc=None, jit=True, chunk=2 ** 33, rc=False, cluster=True, out=None, min_weight=1):
     """:1853-1951: edge weights -> `<qry>_rdbg_weight.xyz` -> mcl (or reuse)
     -> label dictionary -> print the region rows.  The edges, the label
     table, the rows and both texts are made on the device; the host writes
-    the files and runs (or reuses) mcl."""
+    the files and runs (or reuses) mcl.  cluster="cc": instead of running
+    mcl, the built-in clusterer (pg_cluster_cc: edges lighter than min_weight
+    dropped, connected components of the rest) writes the `.mcl`; an existing
+    `.mcl` is reused either way."""
     out = out or sys.stdout
     g = rdbg_dict
     res = rdbg_edges(g, Ns, chunk, rc, brkpt=brkpt, keep_on_device=True)
@@ -263,16 +266,25 @@ def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_
             g.ctx.edges_write(f.fileno())             # formatted on the device, streamed into the file
         else:
             f.write(format_xyz(*res))
+    clustered = False
     if cluster:
         if os.path.isfile("%s.mcl" % oname):
             print("# the mcl has been ran", file=out)
+        elif cluster == "cc":
+            # the label table is made with the clusters: no .mcl parse, no labels_from_edges
+            g.ctx.cluster_cc(None if res is None else res[0], None if res is None else res[1], int(min_weight))
+            with open(oname + ".mcl.tmp", "wb") as f:           # (renamed when whole: the file is reused if present)
+                g.ctx.clusters_write(f.fileno())
+            os.replace(oname + ".mcl.tmp", oname + ".mcl")
+            clustered = True
         else:
             out.flush()
             os.system("mcl %s --abc -I 1.5 -te 8 -o %s.mcl -q x -V all" % (oname, oname))
-    with open(oname + ".mcl", "r") as f:
-        mcl_text = f.read()
-    mk, mv, mi, nxt = host.mcl_labels(mcl_text)              # :1918-1929
-    g.ctx.labels_from_edges(None if res is None else res[0], mk, mv, mi, nxt)     # :1932-1944
+    if not clustered:
+        with open(oname + ".mcl", "r") as f:
+            mcl_text = f.read()
+        mk, mv, mi, nxt = host.mcl_labels(mcl_text)              # :1918-1929
+        g.ctx.labels_from_edges(None if res is None else res[0], mk, mv, mi, nxt)     # :1932-1944
     flags = host.plan_rows(g.seq_len, g.shape, g.buf, int(Ns))
     g.ctx.rows_count(flags, bool(rc))
     names = [bytes(g.buf[int(hs) + 1:int(hs) + int(hl)]) for hs, hl in zip(g.hdr_start, g.hdr_len)]
@@ -311,13 +323,16 @@ def manual_print(out=None):
                  "  -d: the de bruijn graph", "  -r: break point of de bruijn graph",
                  "  -D: the reduced de bruijn graph", "  -R: break point of reduced de bruijn graph",
                  "  -n: length of query sequences for pan-genomic analysis",
-                 "  -c: complementary reverse sequence. 00,01,10,11"):
+                 "  -c: complementary reverse sequence. 00,01,10,11",
+                 "  -a: clustering of the rdBG. mcl (run or reuse mcl) or cc (built-in connected components)",
+                 "  -w: with -a cc, drop edges lighter than this weight. default 1"):
         print(line, file=out)
 
 
 def parse_args(argv):
     """:1983-1997 — same flag handling, including `-k27` and skipped unknowns."""
-    args = {"-i": "", "-k": "50", "-n": "2**63", "-r": "", "-d": "", "-R": "", "-D": "", "-c": "2"}
+    args = {"-i": "", "-k": "50", "-n": "2**63", "-r": "", "-d": "", "-R": "", "-D": "", "-c": "2", "-a": "mcl",
+            "-w": "1"}
     N = len(argv)
     for i in range(1, N):
         k = argv[i]
@@ -333,9 +348,10 @@ def entry_point(argv, out=None, device=0):
     args = parse_args(argv)
     qry, kmer, Ns = args["-i"], int(args["-k"]), host.eval_number(args["-n"])
     bkt, dbs, rbk, rc, rdb = args["-r"], args["-d"], args["-R"], int(args["-c"]), args["-D"]
-    if not qry:
+    if not qry or args["-a"] not in ("mcl", "cc"):
         manual_print(out)
         raise SystemExit()
+    clu = dict(cluster="cc", min_weight=int(args["-w"])) if args["-a"] == "cc" else {}
     chunk = 2 ** 33
     rc0, rc1 = (rc >> 1) == 1, (rc & 1) == 1
     if dbs or rdb:                                    # :2073-2101
@@ -347,7 +363,7 @@ def entry_point(argv, out=None, device=0):
         else:
             rdbg_dict = dbg2rdbg(load_graph(qry, kmer, rdb, device, rdbg=True, rc=rc0))
         print("# find fr", file=out)
-        seq2graph(qry, kmer=kmer, bits=5, Ns=Ns, rdbg_dict=rdbg_dict, chunk=chunk, brkpt=rbk, rc=rc1, out=out)
+        seq2graph(qry, kmer=kmer, bits=5, Ns=Ns, rdbg_dict=rdbg_dict, chunk=chunk, brkpt=rbk, rc=rc1, out=out, **clu)
         return 0
     ctx = Context(min(max(1, kmer), 27), device)     # HIP runtime start-up before the stage timer
     print("# build the dBG", file=out)
@@ -369,7 +385,7 @@ def entry_point(argv, out=None, device=0):
     print("# finished in", time() - st, "seconds", file=out)
     print("# find fr", file=out)
     st = time()
-    seq2graph(qry, kmer=kmer, bits=5, Ns=Ns, rdbg_dict=rdbg_dict, chunk=chunk, brkpt=rbk, rc=rc1, out=out)
+    seq2graph(qry, kmer=kmer, bits=5, Ns=Ns, rdbg_dict=rdbg_dict, chunk=chunk, brkpt=rbk, rc=rc1, out=out, **clu)
     print("# finished in", time() - st, "seconds", file=out)
     return 0
 
