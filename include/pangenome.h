@@ -264,7 +264,9 @@ int pg_edges_format_fd(pg_ctx* ctx, int fd, uint64_t* n_bytes);
  * next_label + 1, ... in order of first appearance (next_label = the number
  * of .mcl lines).  tuples: the edges as the .xyz lists them (n_edges x 4
  * uint64), or NULL for the last pg_edges in first-occurrence order.  The
- * table replaces any pg_set_labels table for the following pg_rows. */
+ * table replaces any pg_set_labels table for the following pg_rows.
+ * PG_EINVAL (before any device work, the context's labels unchanged): a node
+ * value above 2^32 - 1. */
 int pg_labels_from_edges(pg_ctx* ctx, const uint64_t* tuples, uint64_t n_edges, const int64_t* mcl_key,
                          const int64_t* mcl_value, const int64_t* mcl_label, uint64_t n_mcl, int64_t next_label,
                          uint64_t* n_labels);
@@ -309,7 +311,10 @@ int pg_clusters_format_fd(pg_ctx* ctx, int fd, uint64_t* n_bytes);
 
 /* ---- region rows: seqs2path_jit_ (kmer_numba.py:1830-1849) -> seq2path_jit_
  *      (:1523-1573).  Labels are the host-built label_dct (:1918-1944):
- *      (key, value) -> label. */
+ *      (key, value) -> label, distinct (key, value) pairs.  Label -1 is the
+ *      merge's label before a walk's first hit (:1529-1531): as in the
+ *      reference, leading hits labelled -1 open no row and only move the
+ *      next row's start. */
 int pg_set_labels(pg_ctx* ctx, const int64_t* key, const int64_t* value, const int64_t* label, uint64_t n);
 int pg_rows(pg_ctx* ctx, const uint8_t* rec_flags, int rc1, uint64_t* n_rows);
 /* rows: 5 x int64 per row (record index, start, end, strand +1/-1, label),
@@ -318,7 +323,8 @@ int pg_rows_export(pg_ctx* ctx, int64_t* rows5, uint64_t cap);
 /* The text of the last pg_rows, "qid\tstart\tend\t+|-\tlabel\n" per row in
  * print order (:1946-1949), formatted on the device; qid of record r is
  * names[name_off[r] .. name_off[r+1]) (n_names >= records, n_names + 1
- * offsets).  out == NULL: only *n_bytes is set. */
+ * offsets); every call formats with its own names.  out == NULL: only
+ * *n_bytes is set. */
 int pg_rows_format(pg_ctx* ctx, const char* names, const int64_t* name_off, uint64_t n_names, char* out, uint64_t cap,
                    uint64_t* n_bytes);
 /* The same text written to descriptor fd (the reference prints it to

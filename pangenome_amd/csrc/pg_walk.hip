@@ -381,8 +381,10 @@ __global__ void k_lab_insert(const long long* __restrict__ key, const long long*
 // (last <= that predecessor's idx + k), so a walk splits into runs at such
 // hits (and at the walk's first hit, entered with last = 0); one thread
 // resolves each run sequentially.  Rows: the taken hits compacted in walk
-// order; a row starts at a taken hit that is its walk's first or changes the
-// label, and ends at the taken hit before the next row's start.
+// order; a row starts at a taken hit whose label differs from the previous
+// taken one's in its walk (-1 before the walk's first: a walk's leading hits
+// labelled -1 only move the next row's start), and ends at its walk's last
+// taken hit before the next row's start.
 
 // walk of hit j: the last w with seg_off[w] <= j (seg_off: nseg + 1 bounds)
 __device__ __forceinline__ uint32_t walk_of(const unsigned long long* __restrict__ seg_off, uint32_t nseg,
@@ -421,12 +423,12 @@ __global__ void k_row_heads(const Hit* __restrict__ hits, const unsigned long lo
                             uint8_t* __restrict__ head) {
   for (uint64_t a = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; a < na; a += (uint64_t)gridDim.x * blockDim.x) {
     const unsigned long long j = acc[a];
-    bool h = a == 0;
-    if (!h) {
+    long long prev = -1;                       // labels = [-1] at a walk's start (:1529-1531)
+    if (a > 0) {
       const unsigned long long jp = acc[a - 1];
-      h = walk_of(seg_off, nseg, jp) != walk_of(seg_off, nseg, j) || hits[jp].label != hits[j].label;
+      if (walk_of(seg_off, nseg, jp) == walk_of(seg_off, nseg, j)) prev = hits[jp].label;
     }
-    head[a] = h;
+    head[a] = prev != hits[j].label;
   }
 }
 
@@ -439,9 +441,18 @@ __global__ void k_rows(const Hit* __restrict__ hits, const unsigned long long* _
                        const long long* __restrict__ rec_len, int k, long long* __restrict__ rows) {
   for (uint64_t r = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; r < nrows;
        r += (uint64_t)gridDim.x * blockDim.x) {
-    const unsigned long long s = starts[r], e = (r + 1 < nrows ? starts[r + 1] : na) - 1;
-    const unsigned long long js = acc[s], je = acc[e];
+    const unsigned long long s = starts[r];
+    const unsigned long long js = acc[s];
     const uint32_t w = walk_of(seg_off, nseg, js);
+    // the row's last taken hit: before the next row's start and inside this
+    // walk (a following walk's leading hits labelled -1 start no row)
+    unsigned long long lo = s + 1, hi = r + 1 < nrows ? starts[r + 1] : na;
+    const unsigned long long wend = seg_off[w + 1];
+    while (lo < hi) {
+      const unsigned long long mid = (lo + hi) >> 1;
+      if (acc[mid] < wend) lo = mid + 1; else hi = mid;
+    }
+    const unsigned long long je = acc[lo - 1];
     long long start = 0;
     if (s > 0) {
       const unsigned long long jp = acc[s - 1];
@@ -849,6 +860,14 @@ void set_labels(Ctx& c, const int64_t* key, const int64_t* val, const int64_t* i
 // NULL, the last edge pass in first-occurrence order.
 uint64_t labels_from_edges(Ctx& c, const uint64_t* h_tuples, uint64_t n_edges, const int64_t* mk, const int64_t* mv,
                            const int64_t* mi, uint64_t n_mcl, int64_t next_id) {
+  // (node values sort as 32-bit words; a device edge pass's are 16-bit.  Checked
+  // before any device work: a refused call leaves the context's labels alone.)
+  uint64_t maxv = 0xFFFFu;
+  if (h_tuples) {
+    maxv = 0;
+    for (uint64_t i = 0; i < 2 * n_edges; ++i) maxv = std::max<uint64_t>(maxv, h_tuples[2 * i + 1]);
+    if (maxv > 0xFFFFFFFFull) throw Error(-22, "pg_labels_from_edges: node value above 2^32");
+  }
   DevBuf up;
   const unsigned long long* tup;
   if (h_tuples) {
@@ -885,12 +904,7 @@ uint64_t labels_from_edges(Ctx& c, const uint64_t* h_tuples, uint64_t n_edges, c
     auto* sval = val + nn;
     hipLaunchKernelGGL(k_nodes, dim3(grid_for(nn, 256, 8192)), dim3(256), 0, c.stream, tup, nn, key, val, pos);
     PG_HIP(hipGetLastError());
-    uint64_t maxv = 0xFFFFu, maxk = ~0ull;
-    if (h_tuples) {
-      maxv = 0;
-      for (uint64_t i = 0; i < nn; ++i) maxv = std::max<uint64_t>(maxv, h_tuples[2 * i + 1]);
-    }
-    if (maxv > 0xFFFFFFFFull) throw Error(-22, "pg_labels_from_edges: node value above 2^32");
+    const uint64_t maxk = ~0ull;
     sort_pairs(c, val, sval, pos, pos2, nn, bits_for(maxv));          // by value
     hipLaunchKernelGGL(k_gather_key, dim3(grid_for(nn, 256, 8192)), dim3(256), 0, c.stream, key, pos2, nn, tmpk);
     PG_HIP(hipGetLastError());
@@ -989,6 +1003,7 @@ uint64_t walk_rows(Ctx& c, const uint8_t* h_rec_flag, int rc1) {
   starts.reserve(8 * (na + 1));
   const uint64_t nrows = select_flagged(c, idx.as<unsigned long long>(), flag.as<uint8_t>(),
                                         starts.as<unsigned long long>(), na, cnt);
+  if (nrows == 0) return 0;                   // (every taken hit labelled -1)
   c.rows_buf.reserve(40 * (nrows + 1));
   hipLaunchKernelGGL(k_rows, dim3(grid_for(nrows, 256, 16384)), dim3(256), 0, c.stream, hits.as<Hit>(),
                      acc.as<unsigned long long>(), na, starts.as<unsigned long long>(), nrows, d_bounds,
@@ -1012,12 +1027,15 @@ void export_rows(Ctx& c, int64_t* rows5, uint64_t cap) {
 uint64_t format_rows_text(Ctx& c, const char* names, const int64_t* name_off, uint64_t n_names, char* out,
                           uint64_t cap, int fd) {
   const uint64_t n = c.n_rows;
-  if (!c.text_rows) {
+  {
+    // the qids are this call's names: nothing of an earlier call's upload,
+    // line lengths or offsets is reused (one small copy, one kernel and one
+    // scan next to the write)
     c.text_names.reserve(8 * (n_names + 1) + (uint64_t)std::max<int64_t>(name_off[n_names], 0) + 16);
     long long* d_off = c.text_names.as<long long>();
     char* d_names = reinterpret_cast<char*>(d_off + n_names + 1);
     PG_HIP(hipMemcpyAsync(d_off, name_off, 8 * (n_names + 1), hipMemcpyHostToDevice, c.stream));
-    if (name_off[n_names])
+    if (name_off[n_names] > 0)
       PG_HIP(hipMemcpyAsync(d_names, names, (size_t)name_off[n_names], hipMemcpyHostToDevice, c.stream));
     c.text_len.reserve(8 * (n + 1));
     c.text_off.reserve(8 * (n + 1));
@@ -1027,7 +1045,7 @@ uint64_t format_rows_text(Ctx& c, const char* names, const int64_t* name_off, ui
       PG_HIP(hipGetLastError());
     }
     c.text_total = excl_scan_total(c, c.text_len.as<unsigned long long>(), c.text_off.as<unsigned long long>(), n);
-    c.text_rows = true;
+    c.text_rows = true;                       // (text_off now holds the rows' offsets, not the .xyz's)
     c.text_xyz = false;
   }
   if (!out && fd < 0) return c.text_total;
