@@ -332,6 +332,63 @@ int pg_rows_format(pg_ctx* ctx, const char* names, const int64_t* name_off, uint
 int pg_rows_format_fd(pg_ctx* ctx, const char* names, const int64_t* name_off, uint64_t n_names, int fd,
                       uint64_t* n_bytes);
 
+/* ---- frequency table: what the region rows are made for (the reference
+ *      README: "a graph-based method to find the frequency across species";
+ *      its only helper, other/fr_stat.py, reduces a row file to the count,
+ *      max and mean of abs(end - start)).  Per label the genomes it occurs
+ *      in, its occurrences and bases; the spectrum; per genome the core /
+ *      shell / unique bases.  Integer only; the result depends on the input
+ *      alone, whatever the schedule.
+ * Input: rows (record, start, end, strand, label) - the last pg_rows where
+ * they lie on the device (rows5 == NULL; n_rows is then ignored) or n_rows
+ * host rows of 5 x int64 as pg_rows_export returns them - and rec_group
+ * [n_records] int32: the genome of each record, in [0, n_groups), or -1 for
+ * "no genome".  n_groups >= 1; n_groups == 0 only with no rows.
+ * A row is used iff label >= 0 and rec_group[record] >= 0; the others are
+ * skipped and counted in *n_skipped (*n_used: the used ones; *n_labels: the
+ * table's entries; each may be NULL).
+ * PG_EINVAL, before any device work, the previous frequency result kept: a
+ * NULL context; rec_group == NULL; a rec_group entry outside [-1, n_groups);
+ * n_records different from the context's record count when rows5 == NULL; a
+ * host row whose record is outside [0, n_records); rows5 == NULL before any
+ * pg_rows.
+ * The tables are dense in the label: L = 1 + the largest used label, and
+ * L > 2^31 is PG_ERANGE (found by a device reduction before anything is
+ * allocated or replaced).  The pipeline's labels are line and first-appearance
+ * indices, so they are dense.  The dense arrays take (5 + W) x 8 x L device
+ * bytes while the call runs; an allocation failure is PG_ENOMEM with the
+ * previous result kept.
+ * Table: one entry per label with at least one used row, labels ascending:
+ *   n_rows; n_plus, the used rows with strand +1; total_bp = sum of
+ *   |end - start| (unsigned 64-bit; the absolute value as fr_stat.py:14);
+ *   min_len, max_len; the presence set, W = ceil(n_groups / 64) uint64 words
+ *   per entry, genome g being bit g % 64 of word g / 64; n_genomes, its
+ *   popcount.
+ * Spectrum, g in 0..n_groups: labels_by_g[g] = the labels with n_genomes ==
+ * g, bp_by_g[g] = the sum of their total_bp; index 0 is always 0.
+ * Per genome: rows (used rows), bp_total, bp_core (rows whose label has
+ * n_genomes == n_groups), bp_unique (n_genomes == 1 when n_groups > 1: with
+ * one genome everything is core), bp_shell (the rest); bp_core + bp_shell +
+ * bp_unique == bp_total. */
+int pg_freq(pg_ctx* ctx, const int64_t* rows5, uint64_t n_rows, const int32_t* rec_group, uint64_t n_records,
+            uint32_t n_groups, uint64_t* n_labels, uint64_t* n_used, uint64_t* n_skipped);
+/* The table of the last pg_freq in label order; any output pointer may be
+ * NULL; bits takes W words per entry.  cap (entries) below *n_labels is
+ * PG_ERANGE.  This and the four calls below: PG_EINVAL before any pg_freq. */
+int pg_freq_export(pg_ctx* ctx, int64_t* label, uint32_t* n_genomes, uint64_t* n_rows, uint64_t* n_plus,
+                   uint64_t* total_bp, uint64_t* min_len, uint64_t* max_len, uint64_t* bits, uint64_t cap);
+int pg_freq_spectrum(pg_ctx* ctx, uint64_t* labels_by_g, uint64_t* bp_by_g, uint64_t cap);      /* cap >= n_groups + 1 */
+int pg_freq_groups(pg_ctx* ctx, uint64_t* rows, uint64_t* bp_total, uint64_t* bp_core, uint64_t* bp_shell,
+                   uint64_t* bp_unique, uint64_t cap);                                      /* cap >= n_groups     */
+/* The table's text, formatted on the device and kept there like the `.mcl`
+ * text: the header "#label\tgenomes\trows\tplus\tbp\tmin\tmax\n", then one
+ * line of unsigned decimals per entry in table order, '\t'-separated and
+ * '\n'-ended (no entries: the header alone).  out == NULL: only *n_bytes (the
+ * size) is set; otherwise cap >= that size, else PG_ERANGE. */
+int pg_freq_format(pg_ctx* ctx, char* out, uint64_t cap, uint64_t* n_bytes);
+/* The same text written to descriptor fd, as pg_clusters_format_fd writes. */
+int pg_freq_format_fd(pg_ctx* ctx, int fd, uint64_t* n_bytes);
+
 /* ---- text output (host only; no context).  The reference formats these in
  *      Python loops (kmer_numba.py:1893-1904, :1946-1949).
  * pg_format_xyz: "%d_%d\t%d_%d\t%d\n" per edge (tuples as unsigned).
@@ -432,6 +489,10 @@ uint64_t pg_format_rows(const int64_t* rows5, uint64_t n, const char* names, con
  * records (C3: 27.6 M stage A records with 3, 24.2 M with 4, 21.8 M with 8),
  * at a dearer drift search (C3 step: 4 is the fastest). */
 #define PG_TUNE_K3_ANCHORS 20
+/* PG_TUNE_FREQ_FORM: pg_freq's accumulate pass, 0 (default) = rows of one
+ * label aggregated inside each wave before one lane issues the atomics, 1 =
+ * every lane issues its own (the same results; for comparison). */
+#define PG_TUNE_FREQ_FORM 21
 int pg_tune(pg_ctx* ctx, int what, int64_t value);
 
 /* Device bytes the library's buffers hold in this process now (peak == 0)

@@ -35,6 +35,7 @@ PG_TUNE_POISON = 17             # process-wide debug: new device buffers filled 
 PG_TUNE_K1 = 18                 # K1 form bits (bit 0 whole-span pass, bit 1 deeper emission prefetch, bit 2 record table ahead of the emission)
 PG_TUNE_TIMERS = 19             # bits: HIP timing events of K1 / stage A / stages B-C (default 7)
 PG_TUNE_K3_ANCHORS = 20         # packed coverage pass anchors per tile and reference (3-6, 8; 0 = 4)
+PG_TUNE_FREQ_FORM = 21          # pg_freq's accumulate pass: 0 aggregated in the wave, 1 every lane its own atomics
 
 
 class PgStats(C.Structure):
@@ -97,6 +98,12 @@ SIGNATURES = {
     "pg_cluster_cc": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int64, _U64P, _U64P]),
     "pg_clusters_format": (C.c_int, [_P, _P, C.c_uint64, _U64P]),
     "pg_clusters_format_fd": (C.c_int, [_P, C.c_int, _U64P]),
+    "pg_freq": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, C.c_uint32, _U64P, _U64P, _U64P]),
+    "pg_freq_export": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_uint64]),
+    "pg_freq_spectrum": (C.c_int, [_P, _P, _P, C.c_uint64]),
+    "pg_freq_groups": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64]),
+    "pg_freq_format": (C.c_int, [_P, _P, C.c_uint64, _U64P]),
+    "pg_freq_format_fd": (C.c_int, [_P, C.c_int, _U64P]),
     "pg_rows_format": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint64, _U64P]),
     "pg_rows_format_fd": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, _U64P]),
     "pg_get_stats": (C.c_int, [_P, _SP]),
@@ -578,6 +585,80 @@ class Context:
         out = np.empty((n.value, 5), np.int64)
         if n.value:
             check(self.lib.pg_rows_export(self.h, ptr(out), n.value), "pg_rows_export")
+        return out
+
+    # ---------------------------------------------------- frequency table
+    def freq(self, rec_group, n_groups: int, rows=None):
+        """The frequency table (pg_freq) of the last row pass where it lies on
+        the device (rows None) or of host rows [n, 5]; rec_group[r] = record
+        r's genome in [0, n_groups) or -1.  Returns (n_labels, n_used,
+        n_skipped); the table stays on the device (freq_table /
+        freq_spectrum / freq_groups / freq_text / freq_write)."""
+        grp = np.ascontiguousarray(rec_group, dtype=np.int32).reshape(-1)
+        n_records = grp.shape[0]
+        if not n_records:
+            grp = np.full(1, -1, np.int32)           # (never NULL: an empty array's pointer may be)
+        r5, n_rows = None, 0
+        if rows is not None:
+            r5 = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1, 5)
+            n_rows = r5.shape[0]
+            if not n_rows:
+                r5 = np.zeros((1, 5), np.int64)      # (NULL would mean the device rows)
+        nl, nu, ns = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        check(self.lib.pg_freq(self.h, ptr(r5), n_rows, ptr(grp), n_records, int(n_groups),
+                               C.byref(nl), C.byref(nu), C.byref(ns)), "pg_freq")
+        self.n_freq, self.freq_groups_n = nl.value, int(n_groups)
+        return nl.value, nu.value, ns.value
+
+    def freq_table(self) -> dict:
+        """The table of the last freq(): labels, n_genomes, rows, plus, bp,
+        min_len, max_len and the presence bits [n, W] (pg_freq_export)."""
+        n, G = getattr(self, "n_freq", 0), getattr(self, "freq_groups_n", 0)
+        W = (G + 63) // 64
+        t = {"labels": np.empty(n, np.int64), "n_genomes": np.empty(n, np.uint32)}
+        for k in ("rows", "plus", "bp", "min_len", "max_len"):
+            t[k] = np.empty(n, np.uint64)
+        t["bits"] = np.empty((n, W), np.uint64)
+        check(self.lib.pg_freq_export(self.h, *[ptr(t[k]) for k in ("labels", "n_genomes", "rows", "plus", "bp",
+                                                                     "min_len", "max_len", "bits")], n),
+              "pg_freq_export")
+        return t
+
+    def freq_spectrum(self):
+        """(labels_by_g, bp_by_g), uint64 [n_groups + 1] (pg_freq_spectrum)."""
+        nb = getattr(self, "freq_groups_n", 0) + 1
+        a, b = np.empty(nb, np.uint64), np.empty(nb, np.uint64)
+        check(self.lib.pg_freq_spectrum(self.h, ptr(a), ptr(b), nb), "pg_freq_spectrum")
+        return a, b
+
+    def freq_groups(self) -> dict:
+        """Per genome: g_rows, g_bp, g_core, g_shell, g_unique (pg_freq_groups)."""
+        G = getattr(self, "freq_groups_n", 0)
+        names = ("g_rows", "g_bp", "g_core", "g_shell", "g_unique")
+        t = {k: np.empty(G, np.uint64) for k in names}
+        check(self.lib.pg_freq_groups(self.h, *[ptr(t[k]) for k in names], G), "pg_freq_groups")
+        return t
+
+    def freq_text(self) -> bytes:
+        """The table's text, formatted on the device (pg_freq_format)."""
+        n = C.c_uint64()
+        check(self.lib.pg_freq_format(self.h, None, 0, C.byref(n)), "pg_freq_format")
+        buf = np.empty(max(n.value, 1), np.uint8)
+        check(self.lib.pg_freq_format(self.h, ptr(buf), buf.shape[0], C.byref(n)), "pg_freq_format")
+        return buf[:n.value].tobytes()
+
+    def freq_write(self, fd: int) -> int:
+        """freq_text() written straight to descriptor fd at its position
+        (pg_freq_format_fd); flush any buffered writer on fd first."""
+        n = C.c_uint64()
+        check(self.lib.pg_freq_format_fd(self.h, int(fd), C.byref(n)), "pg_freq_format_fd")
+        return n.value
+
+    def rows_export(self, n: int):
+        """The [n, 5] rows of the last rows_count() (pg_rows_export)."""
+        out = np.empty((int(n), 5), np.int64)
+        if n:
+            check(self.lib.pg_rows_export(self.h, ptr(out), int(n)), "pg_rows_export")
         return out
 
 

@@ -94,7 +94,8 @@ void pg_destroy(pg_ctx* x) {
                         &c.recS_mw[1], &c.ctrS, &c.snapA, &c.rseg, &c.k5_ctr, &c.tile_sched, &c.tile_desc, &c.k3_queue,
                         &c.k3_hint, &c.part_cnt, &c.tile_cnt, &c.tile_off, &c.occ, &c.edge_tab, &c.pair_tab,
                         &c.edge_out, &c.edge_exp, &c.lab_tab, &c.lab_list, &c.rows_buf, &c.text_len, &c.text_off,
-                        &c.text_buf, &c.text_names, &c.clu_text, &c.preload,
+                        &c.text_buf, &c.text_names, &c.clu_text, &c.fr_tab, &c.fr_spec, &c.fr_grp, &c.fr_text,
+                        &c.preload,
                         &c.dump_cnt};
   for (auto* b : bufs) b->release();
   pg::pool_destroy(c);
@@ -380,6 +381,10 @@ int pg_tune(pg_ctx* x, int what, int64_t value) {
       case PG_TUNE_POISON:
         if (value < -1 || value > 255) throw pg::Error(PG_EINVAL, "pg_tune: poison byte must be in [-1, 255]");
         pg::DevBytes::poison().store((int)value);
+        break;
+      case PG_TUNE_FREQ_FORM:
+        if (value < 0 || value > 1) throw pg::Error(PG_EINVAL, "pg_tune: frequency pass form must be 0 or 1");
+        x->c.freq_form = (int)value;
         break;
       case PG_TUNE_STAGE_SLOTS:
         if (value < 0 || value == 1 || value > 8) throw pg::Error(PG_EINVAL, "pg_tune: staging slots must be 0 or 2..8");
@@ -701,6 +706,57 @@ int pg_clusters_format_fd(pg_ctx* x, int fd, uint64_t* n_bytes) {
     if (!x->c.clu_ready) throw pg::Error(PG_EINVAL, "pg_clusters_format_fd: no clustering (call pg_cluster_cc first)");
     PG_HIP(hipSetDevice(x->c.device));
     *n_bytes = pg::format_clusters(x->c, nullptr, 0, fd);
+  });
+}
+
+int pg_freq(pg_ctx* x, const int64_t* rows5, uint64_t n_rows, const int32_t* rec_group, uint64_t n_records,
+            uint32_t n_groups, uint64_t* n_labels, uint64_t* n_used, uint64_t* n_skipped) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_freq: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::freq(x->c, rows5, n_rows, rec_group, n_records, n_groups, n_labels, n_used, n_skipped);
+  });
+}
+
+int pg_freq_export(pg_ctx* x, int64_t* label, uint32_t* n_genomes, uint64_t* n_rows, uint64_t* n_plus,
+                   uint64_t* total_bp, uint64_t* min_len, uint64_t* max_len, uint64_t* bits, uint64_t cap) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_freq_export: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::freq_export(x->c, label, n_genomes, n_rows, n_plus, total_bp, min_len, max_len, bits, cap);
+  });
+}
+
+int pg_freq_spectrum(pg_ctx* x, uint64_t* labels_by_g, uint64_t* bp_by_g, uint64_t cap) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_freq_spectrum: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::freq_spectrum(x->c, labels_by_g, bp_by_g, cap);
+  });
+}
+
+int pg_freq_groups(pg_ctx* x, uint64_t* rows, uint64_t* bp_total, uint64_t* bp_core, uint64_t* bp_shell,
+                   uint64_t* bp_unique, uint64_t cap) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_freq_groups: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::freq_groups(x->c, rows, bp_total, bp_core, bp_shell, bp_unique, cap);
+  });
+}
+
+int pg_freq_format(pg_ctx* x, char* out, uint64_t cap, uint64_t* n_bytes) {
+  return guard([&] {
+    if (!x || !n_bytes) throw pg::Error(PG_EINVAL, "pg_freq_format: bad arguments");
+    PG_HIP(hipSetDevice(x->c.device));
+    *n_bytes = pg::format_freq(x->c, out, cap);
+  });
+}
+
+int pg_freq_format_fd(pg_ctx* x, int fd, uint64_t* n_bytes) {
+  return guard([&] {
+    if (!x || !n_bytes || fd < 0) throw pg::Error(PG_EINVAL, "pg_freq_format_fd: bad arguments");
+    PG_HIP(hipSetDevice(x->c.device));
+    *n_bytes = pg::format_freq(x->c, nullptr, 0, fd);
   });
 }
 

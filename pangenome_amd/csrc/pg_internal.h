@@ -82,6 +82,7 @@ struct DevBuf {
     }
   }
   template <class T> T* as() const { return reinterpret_cast<T*>(p); }
+  void swap(DevBuf& o) { std::swap(p, o.p); std::swap(cap, o.cap); }
   void release() {
     if (p) {
       (void)hipFree(p);
@@ -282,6 +283,7 @@ struct Ctx {
   uint64_t n_labels = 0;
   DevBuf rows_buf;                // rows of the last row pass: [n][5] int64
   uint64_t n_rows = 0;
+  bool rows_ready = false;        // a row pass has run (rows_buf / n_rows are its result)
   // text of the last edge or row pass (pg_edges_format / pg_rows_format)
   DevBuf text_len, text_off, text_buf, text_names;
   uint64_t text_total = 0;
@@ -290,6 +292,15 @@ struct Ctx {
   DevBuf clu_text;
   uint64_t clu_total = 0, n_clusters = 0, n_clu_nodes = 0;
   bool clu_ready = false;
+  // ---- frequency table (pg_freq.hip): the result of the last pg_freq
+  DevBuf fr_tab;                  // [n] label, rows, plus, bases, min, max; [n][W] presence words; uint32 [n] genomes
+  DevBuf fr_spec;                 // [2][G + 1]: labels / bases by number of genomes
+  DevBuf fr_grp;                  // [5][G]: rows, bases, core, shell, unique per genome
+  DevBuf fr_text;                 // the table's text
+  uint64_t fr_n = 0, fr_total = 0;
+  uint32_t fr_groups = 0, fr_words = 0;
+  bool fr_ready = false;
+  int freq_form = 0;              // pg_tune: accumulate pass (0 = aggregated in the wave, 1 = every lane its atomics)
 
   // ---- npz persistence (pg_persist.hip)
   DevBuf preload;                 // staged PreEnt pairs, OR-merged by every build
@@ -414,6 +425,18 @@ uint64_t format_rows_text(Ctx& c, const char* names, const int64_t* name_off, ui
 // text on the device for format_clusters.
 void cluster_cc(Ctx& c, const uint64_t* h_tuples, const int64_t* h_counts, uint64_t n_edges, int64_t min_weight);
 uint64_t format_clusters(Ctx& c, char* out, uint64_t cap, int fd = -1);
+
+// pg_freq.hip
+// The frequency table of rows (h_rows5 NULL: the last row pass) grouped by
+// rec_group; replaces the context's previous table only when it succeeds.
+void freq(Ctx& c, const int64_t* h_rows5, uint64_t n_rows, const int32_t* rec_group, uint64_t n_records,
+          uint32_t n_groups, uint64_t* n_labels, uint64_t* n_used, uint64_t* n_skipped);
+void freq_export(Ctx& c, int64_t* label, uint32_t* n_genomes, uint64_t* n_rows, uint64_t* n_plus, uint64_t* total_bp,
+                 uint64_t* min_len, uint64_t* max_len, uint64_t* bits, uint64_t cap);
+void freq_spectrum(Ctx& c, uint64_t* labels_by_g, uint64_t* bp_by_g, uint64_t cap);
+void freq_groups(Ctx& c, uint64_t* rows, uint64_t* bp_total, uint64_t* bp_core, uint64_t* bp_shell,
+                 uint64_t* bp_unique, uint64_t cap);
+uint64_t format_freq(Ctx& c, char* out, uint64_t cap, int fd = -1);
 
 // helpers
 inline uint64_t next_pow2(uint64_t x) {

@@ -970,6 +970,7 @@ uint64_t walk_rows(Ctx& c, const uint8_t* h_rec_flag, int rc1) {
   const uint64_t m = walk_collect<1>(c, P, a, hits, sizeof(Hit), so, sc);
   const uint64_t nseg = so.size();
   c.n_rows = 0;
+  c.rows_ready = true;
   c.text_rows = false;
   if (nseg == 0 || m == 0) return 0;
   // walk bounds (segments are contiguous in walk order)

@@ -1117,8 +1117,18 @@ class GpuShard:
 
     def rows_text(self, labels, flags, rc1, names):
         self.ctx.set_labels(*labels)
-        self.ctx.rows_count(flags, bool(rc1))
+        self.n_rows = self.ctx.rows_count(flags, bool(rc1))
         return self.ctx.rows_text(names)
+
+    def freq(self, rec_group, n_groups):
+        """this rank's partial frequency table of the row pass just run
+        (pg_freq on the device rows); the (label, genome) pairs that
+        host.freq_merge classes a genome's bases by come from the exported rows"""
+        _, used, skipped = self.ctx.freq(rec_group, int(n_groups))
+        t = self.ctx.freq_table()
+        t.update(n_groups=int(n_groups), n_used=used, n_skipped=skipped,
+                 pairs=host.freq_pairs(self.ctx.rows_export(self.n_rows), rec_group, int(n_groups)))
+        return t
 
     def dump_global(self, keys, masks, counts, k, device):
         from ._lib import Context
@@ -1320,10 +1330,23 @@ class DistRun:
         self.reduced = True
 
     # -------------------------------------------------------------- graph
-    def graph(self, Ns, rc1, brkpt="", cluster=True, min_weight=1):
+    def groups(self, Ns, groups):
+        """-g over the whole record table (the same on every rank): the genome
+        of every record and the genome names (host.assign_groups; raises for a
+        group file that misses a record the row pass walks)."""
+        names = [bytes(self.buf[int(s) + 1:int(s) + int(n)]) for s, n in zip(self.S.hdr_start, self.S.hdr_len)]
+        return host.assign_groups(names, host.plan_rows(self.S.seq_len, self.shape, self.buf, int(Ns)), groups)
+
+    def graph(self, Ns, rc1, brkpt="", cluster=True, min_weight=1, groups=None):
         """seq2graph (:1853-1951) over the shards.  cluster="cc": without a
         `.mcl`, rank 0 writes one with the built-in clusterer (on its device,
-        or host.cluster_cc for a backend without one) instead of running mcl."""
+        or host.cluster_cc for a backend without one) instead of running mcl.
+        groups (-g): every rank makes the frequency table of its own rows (on
+        its device, or host.freq_table over its row text for a backend without
+        one) over one global genome numbering; rank 0 merges them and writes
+        the four `<in>_fr_*` files."""
+        if groups:
+            rec_group, gnames = self.groups(Ns, groups)
         loaded, resume = None, None
         if brkpt and os.path.isfile(brkpt):
             offset, lt, lc = host.read_edge_npz(brkpt)
@@ -1386,6 +1409,27 @@ class DistRun:
                     self.out.buffer.flush()
                 else:
                     self.out.write(body.decode())
+        if groups:
+            lg = np.ascontiguousarray(self.S.local(rec_group, self.rank))
+            if hasattr(self.sh, "freq"):
+                part = self.sh.freq(lg, len(gnames))
+            else:
+                part = host.freq_table(host.rows_from_text(text, self.names(), self.S.local(rflags, self.rank)), lg,
+                                       len(gnames))
+            cols = ("labels", "rows", "plus", "bp", "min_len", "max_len", "bits", "pairs")
+            got = self.comm.gather_bytes(_pack(*[np.ascontiguousarray(part[k]).reshape(-1).view(np.uint64)
+                                                 for k in cols], np.array([part["n_used"], part["n_skipped"]], np.uint64)))
+            if self.rank == 0:
+                W = (len(gnames) + 63) // 64
+                tabs = []
+                for p in got:
+                    a = _unpack(p, (np.uint64,) * (len(cols) + 1))
+                    t = dict(zip(cols, a[:-1]), n_used=int(a[-1][0]), n_skipped=int(a[-1][1]))
+                    t["labels"] = t["labels"].view(np.int64)
+                    t["bits"], t["pairs"] = t["bits"].reshape(-1, max(W, 1))[:, :W], t["pairs"].reshape(-1, 4)
+                    tabs.append(t)
+                table = host.freq_merge(tabs, len(gnames))
+                host.write_freq_files(self.qry, lambda f: f.write(host.freq_text(table).encode()), table, gnames)
         self.comm.barrier()
 
 
@@ -1423,12 +1467,16 @@ def entry_point(argv, out=None, shard_factory=None, device=None, dev_index: int 
             manual_print(out)
         raise SystemExit()
     clu = dict(cluster="cc", min_weight=int(args["-w"])) if args["-a"] == "cc" else {}
+    if args["-g"]:
+        clu["groups"] = args["-g"]
     rc0, rc1 = (rc >> 1) == 1, (rc & 1) == 1
     k = min(max(1, kmer), 27)
     shard = shard_factory(k) if shard_factory else GpuShard(k, dev_index)
     comm = Comm(device)
     run = DistRun(qry, k, shard, comm, device=device, out=out, dev_index=dev_index, edge_chunk=edge_chunk,
                   dbg_chunk=dbg_chunk, stream_bases=stream_bases, compact_at=compact_at)
+    if args["-g"] and args["-g"] != "record":
+        run.groups(Ns, args["-g"])                      # a group file is checked before anything is built
     if dbs or rdb:                                      # :2073-2101
         if not rdb:
             run.say("load dBG from disk")

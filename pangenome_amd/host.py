@@ -576,3 +576,236 @@ def merge_edges(loaded_t, loaded_c, tuples, counts, walk_first, segment_of_recor
     out_t = np.array(list(d.keys()), dtype=np.uint64).reshape(-1, 4)
     out_c = np.array(list(d.values()), dtype=np.int64)
     return out_t, out_c
+
+
+# ------------------------------------------------------------ frequency table
+FREQ_HEADER = "#label\tgenomes\trows\tplus\tbp\tmin\tmax\n"
+_U64 = np.uint64
+
+
+def _popcount_rows(bits: np.ndarray) -> np.ndarray:
+    """Set bits of each row of a uint64 [n, W] array."""
+    if bits.shape[0] == 0 or bits.shape[1] == 0:
+        return np.zeros(bits.shape[0], np.uint32)
+    b = np.unpackbits(np.ascontiguousarray(bits).view(np.uint8).reshape(bits.shape[0], -1), axis=1)
+    return b.sum(axis=1).astype(np.uint32)
+
+
+def _freq_derive(t: dict) -> dict:
+    """n_genomes, the spectrum and the per-genome sums of a table from its
+    per-label columns and its (label, genome, rows, bases) pairs."""
+    G = int(t["n_groups"])
+    ng = _popcount_rows(t["bits"])
+    t["n_genomes"] = ng
+    sl, sb = np.zeros(G + 1, _U64), np.zeros(G + 1, _U64)
+    np.add.at(sl, ng, _U64(1))
+    np.add.at(sb, ng, t["bp"])
+    t["spectrum_labels"], t["spectrum_bp"] = sl, sb
+    p = t["pairs"]
+    g = p[:, 1].astype(np.int64)
+    png = ng[np.searchsorted(t["labels"], p[:, 0].astype(np.int64))] if p.shape[0] else np.zeros(0, np.uint32)
+    core = png == G
+    uniq = (png == 1) & ~core
+    for name, sel, col in (("g_rows", slice(None), 2), ("g_bp", slice(None), 3), ("g_core", core, 3),
+                           ("g_unique", uniq, 3)):
+        a = np.zeros(G, _U64)
+        np.add.at(a, g[sel], p[sel, col])
+        t[name] = a
+    t["g_shell"] = t["g_bp"] - t["g_core"] - t["g_unique"]
+    return t
+
+
+def freq_table(rows5, rec_group, n_groups: int) -> dict:
+    """The frequency table's specification (pg_freq computes the same on the
+    device): rows (record, start, end, strand, label) grouped by rec_group
+    (record -> genome in [0, n_groups), or -1).  A row is used iff its label
+    is >= 0 and its record has a genome.  Per label with a used row, labels
+    ascending: rows, plus (strand +1), bp = sum |end - start|, min_len,
+    max_len, the presence bits (uint64 [n, ceil(n_groups / 64)], genome g =
+    bit g % 64 of word g / 64) and n_genomes; spectrum_labels / spectrum_bp
+    [n_groups + 1] by n_genomes; g_rows, g_bp, g_core, g_shell, g_unique per
+    genome (unique only when n_groups > 1); n_used, n_skipped.  `pairs` holds
+    (label, genome, rows, bp) per label and genome, which freq_merge needs to
+    class a genome's bases by labels other ranks saw too."""
+    r = np.ascontiguousarray(rows5, dtype=np.int64).reshape(-1, 5)
+    grp = np.ascontiguousarray(rec_group, dtype=np.int32).reshape(-1)
+    G = int(n_groups)
+    if G < 0 or (G == 0 and r.shape[0]):
+        raise ValueError("freq_table: n_groups is %d with %d rows" % (G, r.shape[0]))
+    if grp.shape[0] and (grp.min() < -1 or grp.max() >= G):
+        raise ValueError("freq_table: a rec_group entry is outside [-1, %d)" % G)
+    if r.shape[0] and (r[:, 0].min() < 0 or r[:, 0].max() >= grp.shape[0]):
+        raise ValueError("freq_table: a row's record is outside [0, %d)" % grp.shape[0])
+    W = (G + 63) // 64
+    g = grp[r[:, 0]].astype(np.int64) if r.shape[0] else np.zeros(0, np.int64)
+    used = (r[:, 4] >= 0) & (g >= 0)
+    u, g = r[used], g[used]
+    s, e = u[:, 1].view(_U64), u[:, 2].view(_U64)
+    length = np.where(u[:, 2] >= u[:, 1], e - s, s - e)
+    labels, inv = np.unique(u[:, 4], return_inverse=True)
+    inv = inv.reshape(-1)
+    n = labels.shape[0]
+    t = {"n_groups": G, "n_used": int(used.sum()), "n_skipped": int(r.shape[0] - used.sum()),
+         "labels": labels.astype(np.int64),
+         "rows": np.bincount(inv, minlength=n).astype(_U64),
+         "plus": np.bincount(inv[u[:, 3] == 1], minlength=n).astype(_U64),
+         "bp": np.zeros(n, _U64), "min_len": np.full(n, ~_U64(0)), "max_len": np.zeros(n, _U64),
+         "bits": np.zeros((n, W), _U64)}
+    np.add.at(t["bp"], inv, length)
+    np.minimum.at(t["min_len"], inv, length)
+    np.maximum.at(t["max_len"], inv, length)
+    np.bitwise_or.at(t["bits"], (inv, g >> 6), _U64(1) << (g & 63).astype(_U64))
+    pk, pinv = np.unique(inv * max(G, 1) + g, return_inverse=True)
+    pinv = pinv.reshape(-1)
+    pairs = np.zeros((pk.shape[0], 4), _U64)
+    pairs[:, 0] = labels[pk // max(G, 1)].astype(_U64)
+    pairs[:, 1] = (pk % max(G, 1)).astype(_U64)
+    pairs[:, 2] = np.bincount(pinv, minlength=pk.shape[0]).astype(_U64)
+    np.add.at(pairs[:, 3], pinv, length)
+    t["pairs"] = pairs
+    return _freq_derive(t)
+
+
+def freq_pairs(rows5, rec_group, n_groups: int) -> np.ndarray:
+    """The (label, genome, rows, bp) pairs of freq_table alone (a shard whose
+    device made the per-label columns adds them for freq_merge)."""
+    return freq_table(rows5, rec_group, n_groups)["pairs"]
+
+
+def freq_text(table: dict) -> str:
+    """The text pg_freq_format writes: the header, then one line per entry."""
+    cols = [table[k].tolist() for k in ("labels", "n_genomes", "rows", "plus", "bp", "min_len", "max_len")]
+    return FREQ_HEADER + "".join("%d\t%d\t%d\t%d\t%d\t%d\t%d\n" % x for x in zip(*cols))
+
+
+def freq_merge(parts: list, n_groups: int) -> dict:
+    """Per-rank tables (freq_table's dicts, over one global genome numbering)
+    merged: rows / plus / bp add, min_len takes the minimum, max_len the
+    maximum, the presence bits are ORed (a genome's records may lie on two
+    ranks), the pairs add; n_genomes, the spectrum and the per-genome sums are
+    derived again from the merged table."""
+    G = int(n_groups)
+    W = (G + 63) // 64
+    lab = np.concatenate([p["labels"] for p in parts]) if parts else np.zeros(0, np.int64)
+    labels, inv = np.unique(lab, return_inverse=True)
+    inv = inv.reshape(-1)
+    n = labels.shape[0]
+    cat = lambda k: np.concatenate([p[k] for p in parts]) if parts else np.zeros(0, _U64)
+    t = {"n_groups": G, "n_used": sum(int(p["n_used"]) for p in parts),
+         "n_skipped": sum(int(p["n_skipped"]) for p in parts), "labels": labels.astype(np.int64),
+         "rows": np.zeros(n, _U64), "plus": np.zeros(n, _U64), "bp": np.zeros(n, _U64),
+         "min_len": np.full(n, ~_U64(0)), "max_len": np.zeros(n, _U64), "bits": np.zeros((n, W), _U64)}
+    for k in ("rows", "plus", "bp"):
+        np.add.at(t[k], inv, cat(k))
+    np.minimum.at(t["min_len"], inv, cat("min_len"))
+    np.maximum.at(t["max_len"], inv, cat("max_len"))
+    if parts and W:
+        np.bitwise_or.at(t["bits"], inv, np.concatenate([p["bits"].reshape(-1, W) for p in parts]))
+    pp = np.concatenate([p["pairs"].reshape(-1, 4) for p in parts]) if parts else np.zeros((0, 4), _U64)
+    pk, pinv = np.unique(pp[:, 0] * _U64(max(G, 1)) + pp[:, 1], return_inverse=True)
+    pinv = pinv.reshape(-1)
+    pairs = np.zeros((pk.shape[0], 4), _U64)
+    pairs[:, 0], pairs[:, 1] = pk // _U64(max(G, 1)), pk % _U64(max(G, 1))
+    np.add.at(pairs[:, 2], pinv, pp[:, 2])
+    np.add.at(pairs[:, 3], pinv, pp[:, 3])
+    t["pairs"] = pairs
+    return _freq_derive(t)
+
+
+def seqid(name: bytes) -> bytes:
+    """A record's id: its header without '>' up to the first whitespace."""
+    p = bytes(name).split(None, 1)
+    return p[0] if p else b""
+
+
+def read_group_file(path: str) -> dict:
+    """`seqid<TAB>genome` lines -> {seqid: genome} (bytes); blank lines and
+    lines starting with '#' are skipped, a later line for a seqid wins."""
+    m = {}
+    with open(path, "rb") as f:
+        for ln in f:
+            ln = ln.rstrip(b"\r\n")
+            if not ln.strip() or ln.startswith(b"#"):
+                continue
+            p = ln.split(b"\t")
+            if len(p) < 2 or not p[1].strip():
+                raise ValueError("%s: not a seqid<TAB>genome line: %r" % (path, ln[:80]))
+            m[p[0].strip()] = p[1].strip()
+    return m
+
+
+def read_groups(path: str, record_ids) -> list:
+    """The genome name of every id in record_ids from a `-g` file; ids the
+    file does not hold are a ValueError naming up to five of them."""
+    m = read_group_file(path)
+    ids = [bytes(x) for x in record_ids]
+    missing = [x for x in ids if x not in m]
+    if missing:
+        raise ValueError("%s: no genome for %d record(s): %s%s" % (
+            path, len(missing), ", ".join(x.decode("utf-8", "replace") for x in missing[:5]),
+            ", ..." if len(missing) > 5 else ""))
+    return [m[x] for x in ids]
+
+
+def assign_groups(names, flags, groups: str):
+    """-g: the genome of every record.  names[r] = record r's header without
+    '>'; flags = the records the row pass walks (plan_rows).  groups ==
+    "record": every walked record is its own genome, named by its seqid;
+    otherwise a `seqid<TAB>genome` file (read_groups).  Genomes are numbered
+    by first appearance over the walked records; the others get -1.  Returns
+    (rec_group int32 [R], genome names)."""
+    walked = np.flatnonzero(np.asarray(flags)).tolist()
+    ids = [seqid(names[r]) for r in walked]
+    gn = ids if groups == "record" else read_groups(groups, ids)
+    rec_group = np.full(len(names), -1, np.int32)
+    number, order = {}, []
+    for r, nm in zip(walked, gn):
+        key = (r, nm) if groups == "record" else nm
+        if key not in number:
+            number[key] = len(order)
+            order.append(nm)
+        rec_group[r] = number[key]
+    return rec_group, order
+
+
+def rows_from_text(text: bytes, names, flags) -> np.ndarray:
+    """The [n, 5] rows of a printed row text whose records are names[r]
+    (a backend without device rows): rows come in record order, so each
+    line's qid is matched forward from the last record seen."""
+    out = []
+    walked = np.flatnonzero(np.asarray(flags)).tolist()
+    w = 0
+    for ln in bytes(text).split(b"\n"):
+        if not ln:
+            continue
+        q, s, e, st, lab = ln.rsplit(b"\t", 4)
+        while w < len(walked) and names[walked[w]] != q:
+            w += 1
+        if w == len(walked):
+            raise ValueError("row text: record %r is not among the walked records in order" % q[:80])
+        out.append((walked[w], int(s), int(e), 1 if st == b"+" else -1, int(lab)))
+    return np.array(out, np.int64).reshape(-1, 5)
+
+
+def write_freq_files(prefix: str, write_text, table: dict, genome_names) -> None:
+    """The four `-g` files of `prefix` (the input's path): `_fr_freq.tsv`
+    (write_text(file) writes the table's text), `_fr_spectrum.tsv`,
+    `_fr_genomes.tsv` and `_fr_presence.npz`; each is written to `.tmp` and
+    renamed when whole."""
+    G = int(table["n_groups"])
+
+    def whole(suffix, fill):
+        fn = prefix + suffix
+        with open(fn + ".tmp", "wb") as f:
+            fill(f)
+        os.replace(fn + ".tmp", fn)
+    whole("_fr_freq.tsv", write_text)
+    sl, sb = table["spectrum_labels"].tolist(), table["spectrum_bp"].tolist()
+    whole("_fr_spectrum.tsv", lambda f: f.write(("#genomes\tlabels\tbp\n" + "".join(
+        "%d\t%d\t%d\n" % (g, sl[g], sb[g]) for g in range(1, G + 1))).encode()))
+    cols = [table[k].tolist() for k in ("g_rows", "g_bp", "g_core", "g_shell", "g_unique")]
+    whole("_fr_genomes.tsv", lambda f: f.write(b"#genome\trows\tbp\tcore\tshell\tunique\n" + b"".join(
+        bytes(nm) + ("\t%d\t%d\t%d\t%d\t%d\n" % x).encode() for nm, x in zip(genome_names, zip(*cols)))))
+    gn = np.array([bytes(x) for x in genome_names], dtype=np.bytes_) if genome_names else np.zeros(0, "S1")
+    whole("_fr_presence.npz", lambda f: np.savez(f, labels=np.asarray(table["labels"], np.int64),
+                                                 bits=np.asarray(table["bits"], _U64), genomes=gn))

@@ -9,7 +9,7 @@ runs in libpangenome_hip.so on an MI355X (pangenome_amd/csrc).  Mirrors:
   dbg2rdbg     :1313-1321                rdBG (K5 degree scan + compaction)
   seq2graph    :1853-1951                edges -> .xyz -> mcl -> labels -> rows
   dump / load_on_disk  :243-335         `<in>_db.npz` (oakht slot layout)
-  entry_point  :1971-2146                CLI (-i -k -n -c -r -d -R -D; ours: -a -w)
+  entry_point  :1971-2146                CLI (-i -k -n -c -r -d -R -D; ours: -a -w -g)
 
 Usage:  python -m pangenome_amd -i genomes.fa -k 27 > result.tab
 """
@@ -149,20 +149,24 @@ class DeviceGraph:
 
 # ------------------------------------------------------------------- passes
 def seq2rdbg(qry, kmer=13, bits=5, Ns=1e6, chunk=2 ** 32, brkpt="./breakpoint", saved="dBG_disk",
-             hashfunc=None, jit=True, rc=True, device=0, ctx=None):
+             hashfunc=None, jit=True, rc=True, device=0, ctx=None, on_parsed=None):
     """:1234-1268.  Returns the device dBG.  An existing `brkpt` npz (-r) is
     the table so far plus the offset to resume at (:1239-1241).  When a pass
     crosses `chunk` bases the reference dumps the table so far to
     `<in>_db_brkpt.npz` (:1255-1259, each dump replacing the last); here the
     last such state is built, dumped and written once, then the whole build
     runs.  `ctx`: a Context to build in (the CLI creates it before its
-    stage timer starts, so the timer excludes HIP runtime start-up)."""
+    stage timer starts, so the timer excludes HIP runtime start-up).
+    `on_parsed(g)`: called once the records are known and before anything is
+    built (-g checks its group file there); the parse and the build are then
+    two calls."""
     if seq_chk(qry) != "fasta":
         raise ValueError("%s: only FASTA input is supported (the reference's FASTQ branch is "
                          "broken, kmer_numba.py:174-186)" % qry)
     mult = 2 if rc else 1
     nbytes = os.path.getsize(qry)
-    if not (brkpt and os.path.isfile(brkpt)) and nbytes * mult <= int(chunk) and not host.ns_hit(nbytes * mult, int(Ns)):
+    if on_parsed is None and not (brkpt and os.path.isfile(brkpt)) and nbytes * mult <= int(chunk) \
+            and not host.ns_hit(nbytes * mult, int(Ns)):
         # no -r resume, and no -n limit or 2^33-base checkpoint can touch a
         # file this size (bases <= bytes): every record is in the pass, so
         # parse and build in one call with the build streamed under the upload
@@ -172,6 +176,8 @@ def seq2rdbg(qry, kmer=13, bits=5, Ns=1e6, chunk=2 ** 32, brkpt="./breakpoint", 
             g.stats = g.ctx.build_dbg(flags, extra, bool(rc))
         return g
     g = DeviceGraph(qry, kmer, device, ctx=ctx)
+    if on_parsed is not None:
+        on_parsed(g)
     resume = None
     if brkpt and os.path.isfile(brkpt):
         offset, keys, values, counts = host.read_db_npz(brkpt)
@@ -198,12 +204,14 @@ def dump(g: DeviceGraph, fn="./tmp"):
     return 0
 
 
-def load_graph(qry, kmer, fn, device=0, rdbg=False, rc=True):
+def load_graph(qry, kmer, fn, device=0, rdbg=False, rc=True, on_parsed=None):
     """load_on_disk (:289-335) into a device graph over `qry`: -d (a dBG,
     reduced next) or -D (rdBG keys: staged with mask 0, so every key passes
     the rdBG rule and membership is exactly the file's key set)."""
     _, keys, values, counts = host.read_db_npz(fn)
     g = DeviceGraph(qry, kmer, device)
+    if on_parsed is not None:
+        on_parsed(g)
     g.ctx.dbg_load(keys, None if rdbg else values, counts)
     g.stats = g.ctx.build_dbg(np.zeros(g.seq_len.shape[0], np.uint8), 0, bool(rc))
     return g
@@ -248,14 +256,17 @@ def rdbg_edges(g: DeviceGraph, Ns, chunk, rc, brkpt="", keep_on_device=False):
 
 
 def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_dict=None, saved=None,
-              hashfunc=None, jit=True, chunk=2 ** 33, rc=False, cluster=True, out=None, min_weight=1):
+              hashfunc=None, jit=True, chunk=2 ** 33, rc=False, cluster=True, out=None, min_weight=1, groups=None):
     """:1853-1951: edge weights -> `<qry>_rdbg_weight.xyz` -> mcl (or reuse)
     -> label dictionary -> print the region rows.  The edges, the label
     table, the rows and both texts are made on the device; the host writes
     the files and runs (or reuses) mcl.  cluster="cc": instead of running
     mcl, the built-in clusterer (pg_cluster_cc: edges lighter than min_weight
     dropped, connected components of the rest) writes the `.mcl`; an existing
-    `.mcl` is reused either way."""
+    `.mcl` is reused either way.  groups (-g; "record" or a `seqid<TAB>genome`
+    file): after the rows are written, their frequency table is made where
+    they lie on the device (pg_freq) and the four `<qry>_fr_*` files written;
+    nothing more is printed."""
     out = out or sys.stdout
     g = rdbg_dict
     res = rdbg_edges(g, Ns, chunk, rc, brkpt=brkpt, keep_on_device=True)
@@ -287,7 +298,7 @@ def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_
         g.ctx.labels_from_edges(None if res is None else res[0], mk, mv, mi, nxt)     # :1932-1944
     flags = host.plan_rows(g.seq_len, g.shape, g.buf, int(Ns))
     g.ctx.rows_count(flags, bool(rc))
-    names = [bytes(g.buf[int(hs) + 1:int(hs) + int(hl)]) for hs, hl in zip(g.hdr_start, g.hdr_len)]
+    names = record_names(g)
     fd = _fileno(out)                                 # print('%s\t%d\t%d\t%s\t%d') (:1946-1949)
     if fd is not None:
         out.flush()
@@ -302,8 +313,38 @@ def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_
                 out.buffer.flush()
             else:
                 out.write(text.decode())
+    if groups:
+        write_freq(g, qry, names, flags, groups)
     gen = g.ctx.label_gen
     return LabelTable(loader=lambda: g.ctx.labels(gen))           # (raises once a later label pass replaced it)
+
+
+def record_names(g):
+    """Every record's header line without '>' (the rows' qid)."""
+    return [bytes(g.buf[int(hs) + 1:int(hs) + int(hl)]) for hs, hl in zip(g.hdr_start, g.hdr_len)]
+
+
+def check_groups(g, Ns, groups):
+    """-g's group file against the records the row pass will walk (raises
+    ValueError for a walked record the file does not name)."""
+    host.assign_groups(record_names(g), host.plan_rows(g.seq_len, g.shape, g.buf, int(Ns)), groups)
+
+
+def write_freq(g, qry, names, flags, groups):
+    """-g: the frequency table of the row pass just run (pg_freq on the
+    device rows) as `<qry>_fr_freq.tsv` (the device text), `_fr_spectrum.tsv`,
+    `_fr_genomes.tsv` and `_fr_presence.npz`."""
+    rec_group, gnames = host.assign_groups(names, flags, groups)
+    g.ctx.freq(rec_group, len(gnames))
+    table = g.ctx.freq_table()
+    table["n_groups"] = len(gnames)
+    table["spectrum_labels"], table["spectrum_bp"] = g.ctx.freq_spectrum()
+    table.update(g.ctx.freq_groups())
+
+    def text(f):
+        f.flush()
+        g.ctx.freq_write(f.fileno())
+    host.write_freq_files(qry, text, table, gnames)
 
 
 def _fileno(out):
@@ -323,6 +364,8 @@ def manual_print(out=None):
                  "  -d: the de bruijn graph", "  -r: break point of de bruijn graph",
                  "  -D: the reduced de bruijn graph", "  -R: break point of reduced de bruijn graph",
                  "  -n: length of query sequences for pan-genomic analysis",
+                 "  -g: frequency table of the regions across genomes. record (each record a genome) or a file of",
+                 "      seqid<TAB>genome lines; writes <in>_fr_freq.tsv, _fr_spectrum.tsv, _fr_genomes.tsv, _fr_presence.npz",
                  "  -c: complementary reverse sequence. 00,01,10,11",
                  "  -a: clustering of the rdBG. mcl (run or reuse mcl) or cc (built-in connected components)",
                  "  -w: with -a cc, drop edges lighter than this weight. default 1"):
@@ -332,7 +375,7 @@ def manual_print(out=None):
 def parse_args(argv):
     """:1983-1997 — same flag handling, including `-k27` and skipped unknowns."""
     args = {"-i": "", "-k": "50", "-n": "2**63", "-r": "", "-d": "", "-R": "", "-D": "", "-c": "2", "-a": "mcl",
-            "-w": "1"}
+            "-w": "1", "-g": ""}
     N = len(argv)
     for i in range(1, N):
         k = argv[i]
@@ -352,23 +395,28 @@ def entry_point(argv, out=None, device=0):
         manual_print(out)
         raise SystemExit()
     clu = dict(cluster="cc", min_weight=int(args["-w"])) if args["-a"] == "cc" else {}
+    grp = args["-g"]
+    if grp:
+        clu["groups"] = grp
+    # a group file is checked against the records before anything is built
+    chk = (lambda g: check_groups(g, Ns, grp)) if grp and grp != "record" else None
     chunk = 2 ** 33
     rc0, rc1 = (rc >> 1) == 1, (rc & 1) == 1
     if dbs or rdb:                                    # :2073-2101
         if not rdb:
             print("load dBG from disk", file=out)
-            kmer_dict = load_graph(qry, kmer, dbs, device, rdbg=False, rc=rc0)
+            kmer_dict = load_graph(qry, kmer, dbs, device, rdbg=False, rc=rc0, on_parsed=chk)
             print("# build the reduced dBG", file=out)
             rdbg_dict = dbg2rdbg(kmer_dict)
         else:
-            rdbg_dict = dbg2rdbg(load_graph(qry, kmer, rdb, device, rdbg=True, rc=rc0))
+            rdbg_dict = dbg2rdbg(load_graph(qry, kmer, rdb, device, rdbg=True, rc=rc0, on_parsed=chk))
         print("# find fr", file=out)
         seq2graph(qry, kmer=kmer, bits=5, Ns=Ns, rdbg_dict=rdbg_dict, chunk=chunk, brkpt=rbk, rc=rc1, out=out, **clu)
         return 0
     ctx = Context(min(max(1, kmer), 27), device)     # HIP runtime start-up before the stage timer
     print("# build the dBG", file=out)
     st = time()
-    kmer_dict = seq2rdbg(qry, kmer, 5, Ns, brkpt=bkt, chunk=chunk, rc=rc0, device=device, ctx=ctx)
+    kmer_dict = seq2rdbg(qry, kmer, 5, Ns, brkpt=bkt, chunk=chunk, rc=rc0, device=device, ctx=ctx, on_parsed=chk)
     print("# finished in", time() - st, "seconds", file=out)
     print("# save dBG to disk", file=out)
     st = time()
