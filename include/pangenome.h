@@ -389,6 +389,47 @@ int pg_freq_format(pg_ctx* ctx, char* out, uint64_t cap, uint64_t* n_bytes);
 /* The same text written to descriptor fd, as pg_clusters_format_fd writes. */
 int pg_freq_format_fd(pg_ctx* ctx, int fd, uint64_t* n_bytes);
 
+/* ---- genome comparison: the two results a pangenome study draws from the
+ *      frequency table's presence sets - how much every pair of genomes
+ *      shares, and how the pan and the core genome change as genomes are
+ *      added (the accumulation or "growth" curves) over several genome
+ *      orders.  Integer only; the result depends on the input alone, whatever
+ *      the schedule.
+ * Input: a presence table bits, uint64 [n_labels][W], W = ceil(n_groups / 64),
+ * genome g being bit g % 64 of word g / 64 as pg_freq_export returns it -
+ * the table of the last pg_freq where it lies on the device (bits == NULL;
+ * n_labels is then ignored and n_groups must equal that table's) or n_labels
+ * host rows of W words.  Label l "is in" genome g iff that bit is set; a row
+ * of zeros is allowed and is in no genome.  orders: int32 [n_orders][n_groups],
+ * every row a permutation of 0 .. n_groups - 1; n_orders >= 0.
+ * Shared: shared[g][h] = the labels in both g and h, uint64 [G][G]; the
+ * diagonal is the number of labels in g; the matrix is symmetric.
+ * Curves, uint64 [P][G] each: for order p and n = 1 .. G let S = the first n
+ * genomes of orders[p]; pan[p][n-1] = the labels in at least one genome of S,
+ * core[p][n-1] = the labels in every genome of S.  So pan[p][G-1] = the
+ * labels with at least one genome, core[p][G-1] = the labels in all G, and
+ * pan[p][0] = core[p][0] = shared[o][o] with o = orders[p][0].
+ * Computed as: the bits transposed to genome-major rows; shared = the
+ * popcount of the AND of two rows; pan / core = the popcounts of the running
+ * OR / AND of the rows taken in the order.
+ * The results stay on the device until the next successful pg_freq_compare;
+ * a successful pg_freq drops them (they described the old table: the two
+ * exports then return PG_EINVAL).
+ * PG_EINVAL, before any device work, the previous result kept: a NULL
+ * context; bits == NULL before any pg_freq or with another n_groups than its
+ * table's; n_groups == 0 with n_labels > 0; orders == NULL with n_orders > 0;
+ * an order row that is not a permutation of 0 .. n_groups - 1; a host row
+ * with a bit at or above n_groups set.  n_groups > 32768 is PG_ERANGE (the
+ * matrix is dense).  An allocation failure is PG_ENOMEM with the previous
+ * result kept.  n_labels == 0 gives all zeros, n_groups == 0 empty results. */
+int pg_freq_compare(pg_ctx* ctx, const uint64_t* bits, uint64_t n_labels, uint32_t n_groups,
+                    const int32_t* orders, uint32_t n_orders);
+/* The results of the last pg_freq_compare: PG_EINVAL before any, PG_ERANGE
+ * for a short cap (in cells).  shared, pan or core may be NULL; with
+ * n_orders == 0 pg_freq_curve succeeds and writes nothing. */
+int pg_freq_shared(pg_ctx* ctx, uint64_t* shared, uint64_t cap);              /* cap >= G * G      */
+int pg_freq_curve(pg_ctx* ctx, uint64_t* pan, uint64_t* core, uint64_t cap);  /* cap >= P * G each */
+
 /* ---- text output (host only; no context).  The reference formats these in
  *      Python loops (kmer_numba.py:1893-1904, :1946-1949).
  * pg_format_xyz: "%d_%d\t%d_%d\t%d\n" per edge (tuples as unsigned).
@@ -493,6 +534,18 @@ uint64_t pg_format_rows(const int64_t* rows5, uint64_t n, const char* names, con
  * label aggregated inside each wave before one lane issues the atomics, 1 =
  * every lane issues its own (the same results; for comparison). */
 #define PG_TUNE_FREQ_FORM 21
+/* PG_TUNE_CMP_CHUNK: pg_freq_compare's shared pass, words (64 labels each) of
+ * the label axis per block, 1 .. 2^25 (a block sums in 32 bits); 0 (default)
+ * = what gives about four blocks per compute unit over the upper triangle of
+ * 64 x 64 genome tiles, in multiples of 32 words and at least 256.  A small
+ * value makes a small input take many chunks and the atomic flush (the same
+ * results). */
+#define PG_TUNE_CMP_CHUNK 22
+/* PG_TUNE_CMP_FORM: pg_freq_compare's curve pass, 0 (default) = per-block LDS
+ * counters flushed once, up to 2048 genomes, and every wave's sums straight
+ * to global atomics above; 1 = the global form at every size (the same
+ * results; for comparison). */
+#define PG_TUNE_CMP_FORM 23
 int pg_tune(pg_ctx* ctx, int what, int64_t value);
 
 /* Device bytes the library's buffers hold in this process now (peak == 0)

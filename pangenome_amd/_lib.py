@@ -36,6 +36,8 @@ PG_TUNE_K1 = 18                 # K1 form bits (bit 0 whole-span pass, bit 1 dee
 PG_TUNE_TIMERS = 19             # bits: HIP timing events of K1 / stage A / stages B-C (default 7)
 PG_TUNE_K3_ANCHORS = 20         # packed coverage pass anchors per tile and reference (3-6, 8; 0 = 4)
 PG_TUNE_FREQ_FORM = 21          # pg_freq's accumulate pass: 0 aggregated in the wave, 1 every lane its own atomics
+PG_TUNE_CMP_CHUNK = 22          # pg_freq_compare's shared pass: label-axis words per block (0 = by size)
+PG_TUNE_CMP_FORM = 23           # pg_freq_compare's curve pass: 0 LDS counters up to 2048 genomes, 1 global atomics
 
 
 class PgStats(C.Structure):
@@ -104,6 +106,9 @@ SIGNATURES = {
     "pg_freq_groups": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64]),
     "pg_freq_format": (C.c_int, [_P, _P, C.c_uint64, _U64P]),
     "pg_freq_format_fd": (C.c_int, [_P, C.c_int, _U64P]),
+    "pg_freq_compare": (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, _P, C.c_uint32]),
+    "pg_freq_shared": (C.c_int, [_P, _P, C.c_uint64]),
+    "pg_freq_curve": (C.c_int, [_P, _P, _P, C.c_uint64]),
     "pg_rows_format": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint64, _U64P]),
     "pg_rows_format_fd": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, _U64P]),
     "pg_get_stats": (C.c_int, [_P, _SP]),
@@ -653,6 +658,45 @@ class Context:
         n = C.c_uint64()
         check(self.lib.pg_freq_format_fd(self.h, int(fd), C.byref(n)), "pg_freq_format_fd")
         return n.value
+
+    # ---------------------------------------------------- genome comparison
+    def freq_compare(self, orders, bits=None, n_groups=None):
+        """The shared-label matrix and the pan / core curves (pg_freq_compare)
+        of the last freq()'s table where it lies on the device (bits None;
+        n_groups defaults to that table's) or of host presence bits [n, W]
+        over n_groups genomes.  orders: int32 [P, n_groups], every row a
+        permutation (None: no order).  The results stay on the device
+        (freq_shared / freq_curves)."""
+        G = int(getattr(self, "freq_groups_n", 0) if n_groups is None else n_groups)
+        o = np.zeros((0, G), np.int32) if orders is None else np.ascontiguousarray(orders, dtype=np.int32)
+        o = o.reshape(-1, G) if G else o.reshape(o.shape[0], 0)
+        P = o.shape[0]
+        b, n = None, 0
+        if bits is not None:
+            b = np.ascontiguousarray(bits, dtype=np.uint64)
+            n = b.shape[0]
+            b = b.reshape(n, (G + 63) // 64)
+            if not b.size:
+                b = np.zeros(1, np.uint64)           # (NULL would mean the device table)
+        if P and not o.size:
+            o = np.zeros(1, np.int32)                # (no genomes: P empty rows, but not NULL)
+        check(self.lib.pg_freq_compare(self.h, ptr(b), n, G, ptr(o) if P else None, P), "pg_freq_compare")
+        self.cmp_groups_n, self.cmp_orders_n = G, P
+
+    def freq_shared(self) -> np.ndarray:
+        """shared[g][h], uint64 [G, G]: the labels in both g and h (pg_freq_shared)."""
+        G = getattr(self, "cmp_groups_n", 0)
+        s = np.empty((G, G), np.uint64)
+        check(self.lib.pg_freq_shared(self.h, ptr(s), G * G), "pg_freq_shared")
+        return s
+
+    def freq_curves(self):
+        """(pan, core), uint64 [P, G]: the labels in at least one / in every
+        one of the first n genomes of each order (pg_freq_curve)."""
+        G, P = getattr(self, "cmp_groups_n", 0), getattr(self, "cmp_orders_n", 0)
+        pan, core = np.empty((P, G), np.uint64), np.empty((P, G), np.uint64)
+        check(self.lib.pg_freq_curve(self.h, ptr(pan), ptr(core), P * G), "pg_freq_curve")
+        return pan, core
 
     def rows_export(self, n: int):
         """The [n, 5] rows of the last rows_count() (pg_rows_export)."""

@@ -95,7 +95,7 @@ void pg_destroy(pg_ctx* x) {
                         &c.k3_hint, &c.part_cnt, &c.tile_cnt, &c.tile_off, &c.occ, &c.edge_tab, &c.pair_tab,
                         &c.edge_out, &c.edge_exp, &c.lab_tab, &c.lab_list, &c.rows_buf, &c.text_len, &c.text_off,
                         &c.text_buf, &c.text_names, &c.clu_text, &c.fr_tab, &c.fr_spec, &c.fr_grp, &c.fr_text,
-                        &c.preload,
+                        &c.cmp_shared, &c.cmp_curve, &c.preload,
                         &c.dump_cnt};
   for (auto* b : bufs) b->release();
   pg::pool_destroy(c);
@@ -385,6 +385,14 @@ int pg_tune(pg_ctx* x, int what, int64_t value) {
       case PG_TUNE_FREQ_FORM:
         if (value < 0 || value > 1) throw pg::Error(PG_EINVAL, "pg_tune: frequency pass form must be 0 or 1");
         x->c.freq_form = (int)value;
+        break;
+      case PG_TUNE_CMP_CHUNK:
+        if (value < 0 || value > (1 << 25)) throw pg::Error(PG_EINVAL, "pg_tune: comparison chunk must be in [0, 2^25]");
+        x->c.cmp_chunk = (uint64_t)value;
+        break;
+      case PG_TUNE_CMP_FORM:
+        if (value < 0 || value > 1) throw pg::Error(PG_EINVAL, "pg_tune: curve pass form must be 0 or 1");
+        x->c.cmp_form = (int)value;
         break;
       case PG_TUNE_STAGE_SLOTS:
         if (value < 0 || value == 1 || value > 8) throw pg::Error(PG_EINVAL, "pg_tune: staging slots must be 0 or 2..8");
@@ -757,6 +765,31 @@ int pg_freq_format_fd(pg_ctx* x, int fd, uint64_t* n_bytes) {
     if (!x || !n_bytes || fd < 0) throw pg::Error(PG_EINVAL, "pg_freq_format_fd: bad arguments");
     PG_HIP(hipSetDevice(x->c.device));
     *n_bytes = pg::format_freq(x->c, nullptr, 0, fd);
+  });
+}
+
+int pg_freq_compare(pg_ctx* x, const uint64_t* bits, uint64_t n_labels, uint32_t n_groups, const int32_t* orders,
+                    uint32_t n_orders) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_freq_compare: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::freq_compare(x->c, bits, n_labels, n_groups, orders, n_orders);
+  });
+}
+
+int pg_freq_shared(pg_ctx* x, uint64_t* shared, uint64_t cap) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_freq_shared: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::freq_shared(x->c, shared, cap);
+  });
+}
+
+int pg_freq_curve(pg_ctx* x, uint64_t* pan, uint64_t* core, uint64_t cap) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_freq_curve: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::freq_curve(x->c, pan, core, cap);
   });
 }
 

@@ -491,6 +491,7 @@ void freq(Ctx& c, const int64_t* h_rows5, uint64_t n_rows, const int32_t* rec_gr
   c.fr_words = W;
   c.fr_total = hdr + body;
   c.fr_ready = true;
+  c.cmp_ready = false;                                     // (a comparison described the old table)
   if (n_labels) *n_labels = nt;
   if (n_used) *n_used = h3[1];
   if (n_skipped) *n_skipped = h3[2];

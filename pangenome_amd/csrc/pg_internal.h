@@ -301,6 +301,13 @@ struct Ctx {
   uint32_t fr_groups = 0, fr_words = 0;
   bool fr_ready = false;
   int freq_form = 0;              // pg_tune: accumulate pass (0 = aggregated in the wave, 1 = every lane its atomics)
+  // ---- genome comparison (pg_compare.hip): the result of the last pg_freq_compare
+  DevBuf cmp_shared;              // uint64 [G][G]: labels shared by every pair of genomes
+  DevBuf cmp_curve;               // uint64 [2][P][G]: pan / core counts per order and number of genomes
+  uint32_t cmp_groups = 0, cmp_orders = 0;
+  bool cmp_ready = false;         // (a successful pg_freq clears it: the result described the old table)
+  uint64_t cmp_chunk = 0;         // pg_tune: label-axis words per k_cmp_shared block (0 = by size)
+  int cmp_form = 0;               // pg_tune: curves (0 = LDS counters up to CMP_LDS_GROUPS genomes, 1 = global atomics)
 
   // ---- npz persistence (pg_persist.hip)
   DevBuf preload;                 // staged PreEnt pairs, OR-merged by every build
@@ -437,6 +444,15 @@ void freq_spectrum(Ctx& c, uint64_t* labels_by_g, uint64_t* bp_by_g, uint64_t ca
 void freq_groups(Ctx& c, uint64_t* rows, uint64_t* bp_total, uint64_t* bp_core, uint64_t* bp_shell,
                  uint64_t* bp_unique, uint64_t cap);
 uint64_t format_freq(Ctx& c, char* out, uint64_t cap, int fd = -1);
+
+// pg_compare.hip
+// Shared-label matrix and pan / core curves over presence bits [n][W] (h_bits
+// NULL: the last freq's table on the device); replaces the context's previous
+// comparison only when it succeeds.
+void freq_compare(Ctx& c, const uint64_t* h_bits, uint64_t n_labels, uint32_t n_groups, const int32_t* orders,
+                  uint32_t n_orders);
+void freq_shared(Ctx& c, uint64_t* shared, uint64_t cap);
+void freq_curve(Ctx& c, uint64_t* pan, uint64_t* core, uint64_t cap);
 
 // helpers
 inline uint64_t next_pow2(uint64_t x) {

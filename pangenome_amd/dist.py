@@ -1130,6 +1130,12 @@ class GpuShard:
                  pairs=host.freq_pairs(self.ctx.rows_export(self.n_rows), rec_group, int(n_groups)))
         return t
 
+    def freq_compare(self, bits, n_groups, orders):
+        """(shared, pan, core) of host presence bits (the merged table's) on
+        this rank's device (pg_freq_compare)"""
+        self.ctx.freq_compare(orders, bits=bits, n_groups=int(n_groups))
+        return (self.ctx.freq_shared(),) + self.ctx.freq_curves()
+
     def dump_global(self, keys, masks, counts, k, device):
         from ._lib import Context
         d = Context(k, device)
@@ -1337,14 +1343,17 @@ class DistRun:
         names = [bytes(self.buf[int(s) + 1:int(s) + int(n)]) for s, n in zip(self.S.hdr_start, self.S.hdr_len)]
         return host.assign_groups(names, host.plan_rows(self.S.seq_len, self.shape, self.buf, int(Ns)), groups)
 
-    def graph(self, Ns, rc1, brkpt="", cluster=True, min_weight=1, groups=None):
+    def graph(self, Ns, rc1, brkpt="", cluster=True, min_weight=1, groups=None, orders=0):
         """seq2graph (:1853-1951) over the shards.  cluster="cc": without a
         `.mcl`, rank 0 writes one with the built-in clusterer (on its device,
         or host.cluster_cc for a backend without one) instead of running mcl.
         groups (-g): every rank makes the frequency table of its own rows (on
         its device, or host.freq_table over its row text for a backend without
         one) over one global genome numbering; rank 0 merges them and writes
-        the four `<in>_fr_*` files."""
+        the four `<in>_fr_*` files.  orders (-p, with groups): rank 0 then
+        compares the genomes over the merged table's presence bits (on its
+        device, or host.freq_compare for a backend without one) and writes the
+        four comparison files."""
         if groups:
             rec_group, gnames = self.groups(Ns, groups)
         loaded, resume = None, None
@@ -1430,6 +1439,11 @@ class DistRun:
                     tabs.append(t)
                 table = host.freq_merge(tabs, len(gnames))
                 host.write_freq_files(self.qry, lambda f: f.write(host.freq_text(table).encode()), table, gnames)
+                if orders:
+                    o = host.compare_orders(len(gnames), int(orders))
+                    cmp = self.sh.freq_compare if hasattr(self.sh, "freq_compare") else host.freq_compare
+                    shared, pan, core = cmp(table["bits"], len(gnames), o)
+                    host.write_compare_files(self.qry, gnames, shared, o, pan, core)
         self.comm.barrier()
 
 
@@ -1457,18 +1471,21 @@ def entry_point(argv, out=None, shard_factory=None, device=None, dev_index: int 
     group; rank 0 prints.  `shard_factory(k)` makes the rank's backend
     (default: GpuShard on dev_index)."""
     import torch.distributed as dist
-    from .kmer import manual_print, parse_args
+    from .kmer import compare_orders_arg, manual_print, parse_args
     out = out or sys.stdout
     args = parse_args(argv)
     qry, kmer, Ns = args["-i"], int(args["-k"]), host.eval_number(args["-n"])
     bkt, dbs, rbk, rc, rdb = args["-r"], args["-d"], args["-R"], int(args["-c"]), args["-D"]
-    if not qry or args["-a"] not in ("mcl", "cc"):
+    n_orders = compare_orders_arg(args)
+    if not qry or args["-a"] not in ("mcl", "cc") or n_orders is None:
         if dist.get_rank() == 0:
             manual_print(out)
         raise SystemExit()
     clu = dict(cluster="cc", min_weight=int(args["-w"])) if args["-a"] == "cc" else {}
     if args["-g"]:
         clu["groups"] = args["-g"]
+    if n_orders:
+        clu["orders"] = n_orders
     rc0, rc1 = (rc >> 1) == 1, (rc & 1) == 1
     k = min(max(1, kmer), 27)
     shard = shard_factory(k) if shard_factory else GpuShard(k, dev_index)

@@ -712,6 +712,120 @@ def freq_merge(parts: list, n_groups: int) -> dict:
     return _freq_derive(t)
 
 
+# ---------------------------------------------------------- genome comparison
+def compare_orders(G: int, P: int) -> np.ndarray:
+    """The genome orders of `-p P`, int32 [P, G]: order 0 is the identity,
+    order p >= 1 a Fisher-Yates shuffle of arange(G) drawn from
+    synth.splitmix64(DEFAULT_SEED, p, G - 1): for t, i in enumerate(G-1 .. 1),
+    j = r[t] % (i + 1) and a[i], a[j] are swapped."""
+    from . import synth
+    G, P = int(G), int(P)
+    out = np.tile(np.arange(G, dtype=np.int32), (P, 1)).reshape(P, G)
+    for p in range(1, P):
+        r = synth.splitmix64(synth.DEFAULT_SEED, p, max(G - 1, 0)).tolist()
+        a = out[p]
+        for t, i in enumerate(range(G - 1, 0, -1)):
+            j = r[t] % (i + 1)
+            a[i], a[j] = a[j], a[i]
+    return out
+
+
+def _popcount_sum(a: np.ndarray) -> np.ndarray:
+    """Set bits of each row of a uint64 [m, w] array, as uint64 [m]."""
+    if hasattr(np, "bitwise_count"):
+        return np.bitwise_count(a).sum(axis=1, dtype=_U64)
+    return _popcount_rows(a).astype(_U64)
+
+
+def freq_compare(bits, n_groups: int, orders):
+    """The genome comparison's specification (pg_freq_compare computes the
+    same on the device).  bits: uint64 [n, W] presence words (genome g = bit
+    g % 64 of word g / 64); orders: int32 [P, G], every row a permutation.
+    Returns (shared, pan, core): shared[g][h] = the labels in both g and h,
+    uint64 [G, G]; pan[p][i] / core[p][i] = the labels in at least one / in
+    every one of the first i + 1 genomes of order p, uint64 [P, G].
+    As the device does: the bits are transposed to genome-major rows (64 Ki
+    labels at a time, whose 0 / 1 matrix also gives that slice's share of
+    `shared` as an exact float32 product), and the curves are the popcounts of
+    the running OR / AND of the rows taken in the order, all orders at once."""
+    G = int(n_groups)
+    W = (G + 63) // 64
+    b = np.ascontiguousarray(bits, dtype=_U64)
+    n = b.shape[0]
+    b = b.reshape(n, W)
+    o = np.ascontiguousarray(orders, dtype=np.int32) if orders is not None else np.zeros((0, G), np.int32)
+    o = o.reshape(-1, G) if G else o.reshape(o.shape[0], 0)
+    P = o.shape[0]
+    if G == 0 and n:
+        raise ValueError("freq_compare: n_groups is 0 with %d labels" % n)
+    if P and G and not np.array_equal(np.sort(o, axis=1), np.tile(np.arange(G, dtype=np.int32), (P, 1))):
+        raise ValueError("freq_compare: an order is not a permutation of 0..%d" % (G - 1))
+    if G & 63 and n and (b[:, W - 1] >> _U64(G & 63)).any():
+        raise ValueError("freq_compare: a row has a bit at or above genome %d" % G)
+    step = 1 << 16
+    NW = (n + 63) // 64
+    T = np.zeros((G, NW), _U64)
+    shared = np.zeros((G, G), _U64)
+    for lo in range(0, n, step):
+        hi = min(lo + step, n)
+        u = np.unpackbits(b[lo:hi].view(np.uint8).reshape(hi - lo, W * 8), axis=1, bitorder="little")[:, :G]
+        f = u.astype(np.float32)
+        shared += (f.T @ f).astype(_U64)                      # (sums below 2^16: exact in float32)
+        ut = np.zeros((G, (hi - lo + 63) // 64 * 64), np.uint8)
+        ut[:, :hi - lo] = u.T
+        T[:, lo // 64:lo // 64 + ut.shape[1] // 64] = np.packbits(ut, axis=1, bitorder="little").view(_U64)
+    pan, core = np.zeros((P, G), _U64), np.zeros((P, G), _U64)
+    if P and G:
+        valid = np.full(NW, ~_U64(0))
+        if n & 63:
+            valid[NW - 1] = (_U64(1) << _U64(n & 63)) - _U64(1)
+        run_or, run_and = np.zeros((P, NW), _U64), np.tile(valid, (P, 1))
+        for i in range(G):
+            x = T[o[:, i]]
+            run_or |= x
+            run_and &= x
+            pan[:, i], core[:, i] = _popcount_sum(run_or), _popcount_sum(run_and)
+    return shared, pan, core
+
+
+def write_compare_files(prefix: str, names, shared, orders, pan, core) -> None:
+    """The four `-p` files of `prefix` (the input's path): `_fr_shared.tsv`
+    (the matrix), `_fr_jaccard.tsv` (1 - shared / union, six decimals; 0 for an
+    empty union), `_fr_curve.tsv` (per number of genomes the sum, minimum and
+    maximum of pan and core over the orders) and `_fr_compare.npz`; each is
+    written to `.tmp` and renamed when whole."""
+    s = np.asarray(shared, _U64)
+    G = s.shape[0]
+    o = np.asarray(orders, np.int32).reshape(-1, G) if G else np.zeros((len(orders), 0), np.int32)
+    pan, core = np.asarray(pan, _U64).reshape(o.shape), np.asarray(core, _U64).reshape(o.shape)
+    nm = [bytes(x) for x in names]
+
+    def whole(suffix, fill):
+        fn = prefix + suffix
+        with open(fn + ".tmp", "wb") as f:
+            fill(f)
+        os.replace(fn + ".tmp", fn)
+    head = b"#genome" + b"".join(b"\t" + x for x in nm) + b"\n"
+    sl = s.tolist()
+    whole("_fr_shared.tsv", lambda f: f.write(head + b"".join(
+        nm[g] + "".join("\t%d" % v for v in sl[g]).encode() + b"\n" for g in range(G))))
+
+    def jac(g, h):
+        u = sl[g][g] + sl[h][h] - sl[g][h]
+        return "\t%.6f" % (1.0 - sl[g][h] / u if u else 0.0)
+    whole("_fr_jaccard.tsv", lambda f: f.write(head + b"".join(
+        nm[g] + "".join(jac(g, h) for h in range(G)).encode() + b"\n" for g in range(G))))
+    P = o.shape[0]
+    cols = [[[int(x) for x in a[:, i].tolist()] for i in range(G)] for a in (pan, core)]
+    stat = lambda v: (sum(v), min(v) if v else 0, max(v) if v else 0)
+    whole("_fr_curve.tsv", lambda f: f.write((
+        "#genomes\torders\tpan_sum\tpan_min\tpan_max\tcore_sum\tcore_min\tcore_max\n" + "".join(
+            "%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\n" % ((i + 1, P) + stat(cols[0][i]) + stat(cols[1][i]))
+            for i in range(G))).encode()))
+    gn = np.array(nm, dtype=np.bytes_) if nm else np.zeros(0, "S1")
+    whole("_fr_compare.npz", lambda f: np.savez(f, genomes=gn, shared=s, orders=o, pan=pan, core=core))
+
+
 def seqid(name: bytes) -> bytes:
     """A record's id: its header without '>' up to the first whitespace."""
     p = bytes(name).split(None, 1)

@@ -9,7 +9,7 @@ runs in libpangenome_hip.so on an MI355X (pangenome_amd/csrc).  Mirrors:
   dbg2rdbg     :1313-1321                rdBG (K5 degree scan + compaction)
   seq2graph    :1853-1951                edges -> .xyz -> mcl -> labels -> rows
   dump / load_on_disk  :243-335         `<in>_db.npz` (oakht slot layout)
-  entry_point  :1971-2146                CLI (-i -k -n -c -r -d -R -D; ours: -a -w -g)
+  entry_point  :1971-2146                CLI (-i -k -n -c -r -d -R -D; ours: -a -w -g -p)
 
 Usage:  python -m pangenome_amd -i genomes.fa -k 27 > result.tab
 """
@@ -256,7 +256,8 @@ def rdbg_edges(g: DeviceGraph, Ns, chunk, rc, brkpt="", keep_on_device=False):
 
 
 def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_dict=None, saved=None,
-              hashfunc=None, jit=True, chunk=2 ** 33, rc=False, cluster=True, out=None, min_weight=1, groups=None):
+              hashfunc=None, jit=True, chunk=2 ** 33, rc=False, cluster=True, out=None, min_weight=1, groups=None,
+              orders=0):
     """:1853-1951: edge weights -> `<qry>_rdbg_weight.xyz` -> mcl (or reuse)
     -> label dictionary -> print the region rows.  The edges, the label
     table, the rows and both texts are made on the device; the host writes
@@ -266,7 +267,9 @@ def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_
     `.mcl` is reused either way.  groups (-g; "record" or a `seqid<TAB>genome`
     file): after the rows are written, their frequency table is made where
     they lie on the device (pg_freq) and the four `<qry>_fr_*` files written;
-    nothing more is printed."""
+    nothing more is printed.  orders (-p, with groups): the genomes are then
+    compared on the device table (pg_freq_compare) over that many genome
+    orders and four more `<qry>_fr_*` files written."""
     out = out or sys.stdout
     g = rdbg_dict
     res = rdbg_edges(g, Ns, chunk, rc, brkpt=brkpt, keep_on_device=True)
@@ -314,7 +317,9 @@ def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_
             else:
                 out.write(text.decode())
     if groups:
-        write_freq(g, qry, names, flags, groups)
+        gnames = write_freq(g, qry, names, flags, groups)
+        if orders:
+            write_compare(g, qry, gnames, int(orders))
     gen = g.ctx.label_gen
     return LabelTable(loader=lambda: g.ctx.labels(gen))           # (raises once a later label pass replaced it)
 
@@ -333,7 +338,7 @@ def check_groups(g, Ns, groups):
 def write_freq(g, qry, names, flags, groups):
     """-g: the frequency table of the row pass just run (pg_freq on the
     device rows) as `<qry>_fr_freq.tsv` (the device text), `_fr_spectrum.tsv`,
-    `_fr_genomes.tsv` and `_fr_presence.npz`."""
+    `_fr_genomes.tsv` and `_fr_presence.npz`.  Returns the genome names."""
     rec_group, gnames = host.assign_groups(names, flags, groups)
     g.ctx.freq(rec_group, len(gnames))
     table = g.ctx.freq_table()
@@ -345,6 +350,18 @@ def write_freq(g, qry, names, flags, groups):
         f.flush()
         g.ctx.freq_write(f.fileno())
     host.write_freq_files(qry, text, table, gnames)
+    return gnames
+
+
+def write_compare(g, qry, gnames, n_orders):
+    """-p: the genomes compared over the frequency table just made, where it
+    lies on the device (pg_freq_compare), in host.compare_orders' orders, as
+    `<qry>_fr_shared.tsv`, `_fr_jaccard.tsv`, `_fr_curve.tsv` and
+    `_fr_compare.npz`."""
+    orders = host.compare_orders(len(gnames), n_orders)
+    g.ctx.freq_compare(orders)
+    pan, core = g.ctx.freq_curves()
+    host.write_compare_files(qry, gnames, g.ctx.freq_shared(), orders, pan, core)
 
 
 def _fileno(out):
@@ -366,6 +383,8 @@ def manual_print(out=None):
                  "  -n: length of query sequences for pan-genomic analysis",
                  "  -g: frequency table of the regions across genomes. record (each record a genome) or a file of",
                  "      seqid<TAB>genome lines; writes <in>_fr_freq.tsv, _fr_spectrum.tsv, _fr_genomes.tsv, _fr_presence.npz",
+                 "  -p: with -g, compare the genomes over this many genome orders (0: off). writes <in>_fr_shared.tsv,",
+                 "      _fr_jaccard.tsv (pairs), _fr_curve.tsv (pan and core genome growth), _fr_compare.npz",
                  "  -c: complementary reverse sequence. 00,01,10,11",
                  "  -a: clustering of the rdBG. mcl (run or reuse mcl) or cc (built-in connected components)",
                  "  -w: with -a cc, drop edges lighter than this weight. default 1"):
@@ -375,7 +394,7 @@ def manual_print(out=None):
 def parse_args(argv):
     """:1983-1997 — same flag handling, including `-k27` and skipped unknowns."""
     args = {"-i": "", "-k": "50", "-n": "2**63", "-r": "", "-d": "", "-R": "", "-D": "", "-c": "2", "-a": "mcl",
-            "-w": "1", "-g": ""}
+            "-w": "1", "-g": "", "-p": "0"}
     N = len(argv)
     for i in range(1, N):
         k = argv[i]
@@ -386,18 +405,31 @@ def parse_args(argv):
     return args
 
 
+def compare_orders_arg(args):
+    """-p's value: the number of genome orders (0: off), or None for a value
+    that is refused - not a non-negative integer, or >= 1 without -g."""
+    try:
+        p = int(args["-p"])
+    except ValueError:
+        return None
+    return None if p < 0 or (p and not args["-g"]) else p
+
+
 def entry_point(argv, out=None, device=0):
     out = out or sys.stdout
     args = parse_args(argv)
     qry, kmer, Ns = args["-i"], int(args["-k"]), host.eval_number(args["-n"])
     bkt, dbs, rbk, rc, rdb = args["-r"], args["-d"], args["-R"], int(args["-c"]), args["-D"]
-    if not qry or args["-a"] not in ("mcl", "cc"):
+    n_orders = compare_orders_arg(args)
+    if not qry or args["-a"] not in ("mcl", "cc") or n_orders is None:
         manual_print(out)
         raise SystemExit()
     clu = dict(cluster="cc", min_weight=int(args["-w"])) if args["-a"] == "cc" else {}
     grp = args["-g"]
     if grp:
         clu["groups"] = grp
+    if n_orders:
+        clu["orders"] = n_orders
     # a group file is checked against the records before anything is built
     chk = (lambda g: check_groups(g, Ns, grp)) if grp and grp != "record" else None
     chunk = 2 ** 33
