@@ -430,6 +430,81 @@ int pg_freq_compare(pg_ctx* ctx, const uint64_t* bits, uint64_t n_labels, uint32
 int pg_freq_shared(pg_ctx* ctx, uint64_t* shared, uint64_t cap);              /* cap >= G * G      */
 int pg_freq_curve(pg_ctx* ctx, uint64_t* pan, uint64_t* core, uint64_t cap);  /* cap >= P * G each */
 
+/* ---- region graph: which region follows which along a genome - the other
+ *      half of a pangenome result next to the frequency table.  Nodes are the
+ *      labels, links the ordered pairs of labels on adjacent rows of one walk,
+ *      paths the walks; the links table's text, and the whole graph as GFA 1.
+ *      Integer only; the result depends on the input alone, whatever the
+ *      schedule.
+ * Input: exactly pg_freq's - rows (record, start, end, strand, label), the
+ * last pg_rows where they lie on the device (rows5 == NULL; n_rows is then
+ * ignored) or n_rows host rows of 5 x int64, and rec_group [n_records] int32
+ * in [-1, n_groups).  A row is used iff label >= 0 and rec_group[record] >= 0;
+ * the others are counted in *n_skipped (every count pointer may be NULL).
+ * Run (one path): a maximal stretch of rows that are consecutive in the list,
+ * all used, and equal in record and in strand (equal values); an unused row,
+ * a new record or a new strand ends it; one row is a path of one step.  For
+ * the rows of pg_rows a run is one walk of one record on one strand.
+ * Link (a, b): two rows adjacent in a run, a the earlier row's label and b the
+ * later one's - walk order; no orientation is inferred and a == b is a legal
+ * link.  count = the adjacent pairs over all runs, n_genomes = the distinct
+ * rec_group[record] among them.
+ * Node: every label with a used row: n_rows, its used rows; max_len, the
+ * largest |end - start| of them (unsigned 64-bit, as pg_freq); n_out / n_in,
+ * the distinct links leaving / entering it.
+ * Order: nodes by label ascending, links by (a, b) ascending, paths in list
+ * order.
+ * PG_EINVAL, before any device work, the previous region graph kept: pg_freq's
+ * list - a NULL context; rec_group == NULL; a rec_group entry outside
+ * [-1, n_groups); n_records different from the context's record count when
+ * rows5 == NULL; a host row whose record is outside [0, n_records);
+ * rows5 == NULL before any pg_rows; n_groups == 0 with rows.
+ * The tables are dense in the label: L = 1 + the largest used label, and
+ * L > 2^31 is PG_ERANGE (found by a device reduction before anything is
+ * allocated or replaced).  The dense arrays take 24 x L device bytes while the
+ * call runs, the link pass 32 bytes per adjacent pair; an allocation failure
+ * is PG_ENOMEM with the previous graph kept.
+ * The graph stays on the device until the next successful pg_region_graph;
+ * pg_freq and pg_freq_compare neither read nor drop it, nor it theirs. */
+int pg_region_graph(pg_ctx* ctx, const int64_t* rows5, uint64_t n_rows, const int32_t* rec_group,
+                    uint64_t n_records, uint32_t n_groups, uint64_t* n_nodes, uint64_t* n_links, uint64_t* n_paths,
+                    uint64_t* n_skipped);
+/* The three tables of the last pg_region_graph; any output pointer may be
+ * NULL; cap (entries) below the table's size is PG_ERANGE.  These and the
+ * four text calls below: PG_EINVAL before any pg_region_graph.
+ * Paths: for the run's first row f and last row z, lo = min(f.start, z.start)
+ * and hi = max(f.end, z.end) (the run's span for the rows of pg_rows, on
+ * either strand); n_steps, its rows; strand, the value the rows carry. */
+int pg_region_nodes(pg_ctx* ctx, int64_t* label, uint64_t* n_rows, uint64_t* max_len, uint32_t* n_out,
+                    uint32_t* n_in, uint64_t cap);
+int pg_region_links(pg_ctx* ctx, int64_t* from, int64_t* to, uint64_t* count, uint32_t* n_genomes, uint64_t cap);
+int pg_region_paths(pg_ctx* ctx, int64_t* record, int64_t* strand, int64_t* lo, int64_t* hi, uint64_t* n_steps,
+                    uint64_t cap);
+/* The links table's text, formatted on the device and kept there like
+ * pg_freq_format's: the header "#from\tto\tcount\tgenomes\n", then one
+ * "%d\t%d\t%d\t%d\n" line per link in table order (no links: the header
+ * alone).  out == NULL: only *n_bytes (the size) is set; otherwise cap >= that
+ * size, else PG_ERANGE.  The _fd form writes as pg_freq_format_fd does. */
+int pg_region_links_format(pg_ctx* ctx, char* out, uint64_t cap, uint64_t* n_bytes);
+int pg_region_links_format_fd(pg_ctx* ctx, int fd, uint64_t* n_bytes);
+/* The graph as GFA 1, formatted on the device by every call with its own
+ * names (names[name_off[r] .. name_off[r+1]) is record r's, copied verbatim,
+ * as pg_rows_format takes them), in this order:
+ *   H\tVN:Z:1.0\n
+ *   S\t<label>\t*\tLN:i:<max_len>\n                              per node
+ *   L\t<a>\t+\t<b>\t+\t0M\tRC:i:<count>\tgn:i:<n_genomes>\n      per link
+ *   P\t<name>:<lo>-<hi>:<+|->\t<label>+,<label>+,...\t*\n        per path
+ * the sign being + iff the strand equals 1, as pg_rows_format prints it.  No
+ * segment sequences: `*` plus LN is valid GFA 1.  With no rows the text is the
+ * H line alone.  n_names below the context's record count - with host rows:
+ * below 1 + the largest record of a used row - is PG_EINVAL, as is a NULL or
+ * descending name_off.  out == NULL: only *n_bytes is set; otherwise cap >=
+ * that size, else PG_ERANGE.  The _fd form writes as pg_rows_format_fd does. */
+int pg_region_gfa(pg_ctx* ctx, const char* names, const int64_t* name_off, uint64_t n_names, char* out,
+                  uint64_t cap, uint64_t* n_bytes);
+int pg_region_gfa_fd(pg_ctx* ctx, const char* names, const int64_t* name_off, uint64_t n_names, int fd,
+                     uint64_t* n_bytes);
+
 /* ---- text output (host only; no context).  The reference formats these in
  *      Python loops (kmer_numba.py:1893-1904, :1946-1949).
  * pg_format_xyz: "%d_%d\t%d_%d\t%d\n" per edge (tuples as unsigned).

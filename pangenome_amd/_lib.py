@@ -109,6 +109,14 @@ SIGNATURES = {
     "pg_freq_compare": (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, _P, C.c_uint32]),
     "pg_freq_shared": (C.c_int, [_P, _P, C.c_uint64]),
     "pg_freq_curve": (C.c_int, [_P, _P, _P, C.c_uint64]),
+    "pg_region_graph": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, C.c_uint32, _U64P, _U64P, _U64P, _U64P]),
+    "pg_region_nodes": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64]),
+    "pg_region_links": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64]),
+    "pg_region_paths": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64]),
+    "pg_region_links_format": (C.c_int, [_P, _P, C.c_uint64, _U64P]),
+    "pg_region_links_format_fd": (C.c_int, [_P, C.c_int, _U64P]),
+    "pg_region_gfa": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint64, _U64P]),
+    "pg_region_gfa_fd": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, _U64P]),
     "pg_rows_format": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint64, _U64P]),
     "pg_rows_format_fd": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, _U64P]),
     "pg_get_stats": (C.c_int, [_P, _SP]),
@@ -697,6 +705,94 @@ class Context:
         pan, core = np.empty((P, G), np.uint64), np.empty((P, G), np.uint64)
         check(self.lib.pg_freq_curve(self.h, ptr(pan), ptr(core), P * G), "pg_freq_curve")
         return pan, core
+
+    # ---------------------------------------------------- region graph
+    def region_graph(self, rec_group, n_groups: int, rows=None):
+        """The region graph (pg_region_graph) of the last row pass where it
+        lies on the device (rows None) or of host rows [n, 5]; rec_group as
+        freq() takes it.  Returns (n_nodes, n_links, n_paths, n_skipped); the
+        graph stays on the device (region_nodes / region_links / region_paths
+        / region_links_text / region_gfa_text and their _write forms)."""
+        grp = np.ascontiguousarray(rec_group, dtype=np.int32).reshape(-1)
+        n_records = grp.shape[0]
+        if not n_records:
+            grp = np.full(1, -1, np.int32)           # (never NULL: an empty array's pointer may be)
+        r5, n_rows = None, 0
+        if rows is not None:
+            r5 = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1, 5)
+            n_rows = r5.shape[0]
+            if not n_rows:
+                r5 = np.zeros((1, 5), np.int64)      # (NULL would mean the device rows)
+        nn, nl, npth, ns = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        check(self.lib.pg_region_graph(self.h, ptr(r5), n_rows, ptr(grp), n_records, int(n_groups),
+                                       C.byref(nn), C.byref(nl), C.byref(npth), C.byref(ns)), "pg_region_graph")
+        self.n_region = (nn.value, nl.value, npth.value)
+        return nn.value, nl.value, npth.value, ns.value
+
+    def region_nodes(self) -> dict:
+        """The nodes of the last region_graph(), labels ascending: labels,
+        rows, max_len, n_out, n_in (pg_region_nodes)."""
+        n = getattr(self, "n_region", (0, 0, 0))[0]
+        t = {"labels": np.empty(n, np.int64), "rows": np.empty(n, np.uint64), "max_len": np.empty(n, np.uint64),
+             "n_out": np.empty(n, np.uint32), "n_in": np.empty(n, np.uint32)}
+        check(self.lib.pg_region_nodes(self.h, *[ptr(t[k]) for k in ("labels", "rows", "max_len", "n_out", "n_in")],
+                                       n), "pg_region_nodes")
+        return t
+
+    def region_links(self) -> dict:
+        """The links by (from, to) ascending: link_from, link_to, link_count,
+        link_genomes (pg_region_links)."""
+        n = getattr(self, "n_region", (0, 0, 0))[1]
+        t = {"link_from": np.empty(n, np.int64), "link_to": np.empty(n, np.int64),
+             "link_count": np.empty(n, np.uint64), "link_genomes": np.empty(n, np.uint32)}
+        check(self.lib.pg_region_links(self.h, *[ptr(t[k]) for k in ("link_from", "link_to", "link_count",
+                                                                      "link_genomes")], n), "pg_region_links")
+        return t
+
+    def region_paths(self) -> dict:
+        """The paths in list order: path_record, path_strand, path_lo,
+        path_hi, path_steps (pg_region_paths)."""
+        n = getattr(self, "n_region", (0, 0, 0))[2]
+        t = {k: np.empty(n, np.int64) for k in ("path_record", "path_strand", "path_lo", "path_hi")}
+        t["path_steps"] = np.empty(n, np.uint64)
+        check(self.lib.pg_region_paths(self.h, *[ptr(t[k]) for k in ("path_record", "path_strand", "path_lo",
+                                                                      "path_hi", "path_steps")], n), "pg_region_paths")
+        return t
+
+    def region_links_text(self) -> bytes:
+        """The links table's text, formatted on the device (pg_region_links_format)."""
+        n = C.c_uint64()
+        check(self.lib.pg_region_links_format(self.h, None, 0, C.byref(n)), "pg_region_links_format")
+        buf = np.empty(max(n.value, 1), np.uint8)
+        check(self.lib.pg_region_links_format(self.h, ptr(buf), buf.shape[0], C.byref(n)), "pg_region_links_format")
+        return buf[:n.value].tobytes()
+
+    def region_links_write(self, fd: int) -> int:
+        """region_links_text() written straight to descriptor fd at its
+        position (pg_region_links_format_fd); flush any buffered writer on fd first."""
+        n = C.c_uint64()
+        check(self.lib.pg_region_links_format_fd(self.h, int(fd), C.byref(n)), "pg_region_links_format_fd")
+        return n.value
+
+    def region_gfa_text(self, names: list) -> bytes:
+        """The graph as GFA 1, formatted on the device (pg_region_gfa);
+        names[r] = record r's name in the path lines."""
+        nb, off = _names_blob(names)
+        n = C.c_uint64()
+        check(self.lib.pg_region_gfa(self.h, ptr(nb), ptr(off), len(names), None, 0, C.byref(n)), "pg_region_gfa")
+        buf = np.empty(max(n.value, 1), np.uint8)
+        check(self.lib.pg_region_gfa(self.h, ptr(nb), ptr(off), len(names), ptr(buf), buf.shape[0], C.byref(n)),
+              "pg_region_gfa")
+        return buf[:n.value].tobytes()
+
+    def region_gfa_write(self, names: list, fd: int) -> int:
+        """region_gfa_text(names) written straight to descriptor fd at its
+        position (pg_region_gfa_fd); flush any buffered writer on fd first."""
+        nb, off = _names_blob(names)
+        n = C.c_uint64()
+        check(self.lib.pg_region_gfa_fd(self.h, ptr(nb), ptr(off), len(names), int(fd), C.byref(n)),
+              "pg_region_gfa_fd")
+        return n.value
 
     def rows_export(self, n: int):
         """The [n, 5] rows of the last rows_count() (pg_rows_export)."""

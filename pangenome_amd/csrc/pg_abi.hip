@@ -95,7 +95,8 @@ void pg_destroy(pg_ctx* x) {
                         &c.k3_hint, &c.part_cnt, &c.tile_cnt, &c.tile_off, &c.occ, &c.edge_tab, &c.pair_tab,
                         &c.edge_out, &c.edge_exp, &c.lab_tab, &c.lab_list, &c.rows_buf, &c.text_len, &c.text_off,
                         &c.text_buf, &c.text_names, &c.clu_text, &c.fr_tab, &c.fr_spec, &c.fr_grp, &c.fr_text,
-                        &c.cmp_shared, &c.cmp_curve, &c.preload,
+                        &c.cmp_shared, &c.cmp_curve, &c.rg_nodes, &c.rg_links, &c.rg_paths, &c.rg_steps, &c.rg_text,
+                        &c.preload,
                         &c.dump_cnt};
   for (auto* b : bufs) b->release();
   pg::pool_destroy(c);
@@ -790,6 +791,76 @@ int pg_freq_curve(pg_ctx* x, uint64_t* pan, uint64_t* core, uint64_t cap) {
     if (!x) throw pg::Error(PG_EINVAL, "pg_freq_curve: ctx is NULL");
     PG_HIP(hipSetDevice(x->c.device));
     pg::freq_curve(x->c, pan, core, cap);
+  });
+}
+
+int pg_region_graph(pg_ctx* x, const int64_t* rows5, uint64_t n_rows, const int32_t* rec_group, uint64_t n_records,
+                    uint32_t n_groups, uint64_t* n_nodes, uint64_t* n_links, uint64_t* n_paths,
+                    uint64_t* n_skipped) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_region_graph: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::region_graph(x->c, rows5, n_rows, rec_group, n_records, n_groups, n_nodes, n_links, n_paths, n_skipped);
+  });
+}
+
+int pg_region_nodes(pg_ctx* x, int64_t* label, uint64_t* n_rows, uint64_t* max_len, uint32_t* n_out, uint32_t* n_in,
+                    uint64_t cap) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_region_nodes: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::region_nodes(x->c, label, n_rows, max_len, n_out, n_in, cap);
+  });
+}
+
+int pg_region_links(pg_ctx* x, int64_t* from, int64_t* to, uint64_t* count, uint32_t* n_genomes, uint64_t cap) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_region_links: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::region_links(x->c, from, to, count, n_genomes, cap);
+  });
+}
+
+int pg_region_paths(pg_ctx* x, int64_t* record, int64_t* strand, int64_t* lo, int64_t* hi, uint64_t* n_steps,
+                    uint64_t cap) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_region_paths: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::region_paths(x->c, record, strand, lo, hi, n_steps, cap);
+  });
+}
+
+int pg_region_links_format(pg_ctx* x, char* out, uint64_t cap, uint64_t* n_bytes) {
+  return guard([&] {
+    if (!x || !n_bytes) throw pg::Error(PG_EINVAL, "pg_region_links_format: bad arguments");
+    PG_HIP(hipSetDevice(x->c.device));
+    *n_bytes = pg::format_region_links(x->c, out, cap);
+  });
+}
+
+int pg_region_links_format_fd(pg_ctx* x, int fd, uint64_t* n_bytes) {
+  return guard([&] {
+    if (!x || !n_bytes || fd < 0) throw pg::Error(PG_EINVAL, "pg_region_links_format_fd: bad arguments");
+    PG_HIP(hipSetDevice(x->c.device));
+    *n_bytes = pg::format_region_links(x->c, nullptr, 0, fd);
+  });
+}
+
+int pg_region_gfa(pg_ctx* x, const char* names, const int64_t* name_off, uint64_t n_names, char* out, uint64_t cap,
+                  uint64_t* n_bytes) {
+  return guard([&] {
+    if (!x || !n_bytes) throw pg::Error(PG_EINVAL, "pg_region_gfa: bad arguments");
+    PG_HIP(hipSetDevice(x->c.device));
+    *n_bytes = pg::format_region_gfa(x->c, names, name_off, n_names, out, cap);
+  });
+}
+
+int pg_region_gfa_fd(pg_ctx* x, const char* names, const int64_t* name_off, uint64_t n_names, int fd,
+                     uint64_t* n_bytes) {
+  return guard([&] {
+    if (!x || !n_bytes || fd < 0) throw pg::Error(PG_EINVAL, "pg_region_gfa_fd: bad arguments");
+    PG_HIP(hipSetDevice(x->c.device));
+    *n_bytes = pg::format_region_gfa(x->c, names, name_off, n_names, nullptr, 0, fd);
   });
 }
 

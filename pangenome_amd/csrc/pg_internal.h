@@ -308,6 +308,15 @@ struct Ctx {
   bool cmp_ready = false;         // (a successful pg_freq clears it: the result described the old table)
   uint64_t cmp_chunk = 0;         // pg_tune: label-axis words per k_cmp_shared block (0 = by size)
   int cmp_form = 0;               // pg_tune: curves (0 = LDS counters up to CMP_LDS_GROUPS genomes, 1 = global atomics)
+  // ---- region graph (pg_region.hip): the result of the last pg_region_graph
+  DevBuf rg_nodes;                // [n] label, rows, max length; uint32 [n] links out, links in
+  DevBuf rg_links;                // [n] from, to, count; uint32 [n] genomes
+  DevBuf rg_paths;                // [n] record, strand, lo, hi, steps, first step
+  DevBuf rg_steps;                // the used rows in list order: [n] label; uint8 [n] first / last of its path
+  DevBuf rg_text;                 // the links table's text
+  uint64_t rg_nn = 0, rg_nl = 0, rg_np = 0, rg_nu = 0, rg_total = 0;
+  uint64_t rg_names = 0;          // record names a GFA text needs
+  bool rg_ready = false;
 
   // ---- npz persistence (pg_persist.hip)
   DevBuf preload;                 // staged PreEnt pairs, OR-merged by every build
@@ -453,6 +462,21 @@ void freq_compare(Ctx& c, const uint64_t* h_bits, uint64_t n_labels, uint32_t n_
                   uint32_t n_orders);
 void freq_shared(Ctx& c, uint64_t* shared, uint64_t cap);
 void freq_curve(Ctx& c, uint64_t* pan, uint64_t* core, uint64_t cap);
+
+// pg_region.hip
+// The region graph of rows (h_rows5 NULL: the last row pass) grouped by
+// rec_group: nodes, links and paths; replaces the context's previous graph
+// only when it succeeds.
+void region_graph(Ctx& c, const int64_t* h_rows5, uint64_t n_rows, const int32_t* rec_group, uint64_t n_records,
+                  uint32_t n_groups, uint64_t* n_nodes, uint64_t* n_links, uint64_t* n_paths, uint64_t* n_skipped);
+void region_nodes(Ctx& c, int64_t* label, uint64_t* n_rows, uint64_t* max_len, uint32_t* n_out, uint32_t* n_in,
+                  uint64_t cap);
+void region_links(Ctx& c, int64_t* from, int64_t* to, uint64_t* count, uint32_t* n_genomes, uint64_t cap);
+void region_paths(Ctx& c, int64_t* record, int64_t* strand, int64_t* lo, int64_t* hi, uint64_t* n_steps,
+                  uint64_t cap);
+uint64_t format_region_links(Ctx& c, char* out, uint64_t cap, int fd = -1);
+uint64_t format_region_gfa(Ctx& c, const char* names, const int64_t* name_off, uint64_t n_names, char* out,
+                           uint64_t cap, int fd = -1);
 
 // helpers
 inline uint64_t next_pow2(uint64_t x) {

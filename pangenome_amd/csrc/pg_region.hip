@@ -1,0 +1,775 @@
+// pg_region.hip — the region graph of the region rows: which region follows
+// which along a genome.  Nodes are the labels, links the ordered pairs of
+// labels on adjacent rows of one walk, paths the walks themselves; the links
+// table's text and the whole graph as GFA 1.
+//
+// Rows are (record, start, end, strand, label); rec_group maps a record to
+// its genome (or -1).  A row is used iff label >= 0 and its record has a
+// genome (pg_freq's rule).  A run is a maximal stretch of consecutive used
+// rows of one record and strand; a link (a, b) is two adjacent rows of a run.
+// Tables are dense in the label (L = 1 + the largest used label).
+//
+// Steps, each its own launch on c.stream (no hand-shake inside a kernel):
+//   a. k_rg_scan    per row a flag byte (used, run head); the largest used
+//                   label and record, the used and the skipped rows.  The row
+//                   before a tile's first one is loaded with the tile (one
+//                   halo row), so a run that crosses a tile is not cut.
+//      two scans of the flag bits: used rows / run heads before every row
+//      (the step index and the run id of a row)
+//   b. k_rg_emit    per used row its step (label, first / last of its run);
+//                   run heads and tails fill the path table; every other used
+//                   row emits the pair key a << lb | b and its genome
+//   c. two stable radix sorts (by genome, then by key) give (key, genome)
+//      order; k_rg_lflags marks where the key and where (key, genome) change,
+//      two scans number the links and count the changes, k_rg_links /
+//      k_rg_linkfin fill from, to, count and n_genomes
+//   d. k_rg_accum   rows and max length per label, k_rg_degree the distinct
+//                   links leaving and entering it, into dense arrays with
+//                   integer atomics at agent scope; select + k_rg_gather the
+//                   labels seen
+//   e. k_rg_llen / k_rg_lwrite   the links text, kept on the device;
+//      k_rg_glen / k_rg_gwrite   the GFA text, made by every call with its
+//                   own names: one thread per S line, L line and path step
+//                   (a path's header belongs to its first step, its trailer
+//                   to its last: no thread walks a path)
+//
+// Contention (d): at a low weight cut one label holds every other row (rows
+// A b A c A d ..., see pg_freq.hip) and is an end of most links.  Each wave
+// therefore aggregates first, as k_fr_accum does: it takes the label of its
+// first unserved lane, ballots the lanes that share it, and one lane issues
+// the atomics.  Links are sorted by (a, b), so the lanes of a wave share a.
+//
+// Every sum is an integer and every atomic commutes: the result depends on
+// the input alone, whatever the schedule.
+#include <cstring>
+
+#include "pg_internal.h"
+#include "pg_prim.h"
+
+namespace pg {
+
+typedef unsigned long long ull;
+
+#define RG_BLOCK 256
+#define RG_AGG_MIN 4               // lanes of a wave sharing a label before one lane issues for them
+
+#define RG_USED 1u                 // flag byte of a row: it is used
+#define RG_HEAD 2u                 //                     it starts a run
+#define RG_FIRST 1u                // flag byte of a step: first of its path
+#define RG_LAST 2u                 //                      last of its path
+#define RG_LINK 1u                 // flag byte of a sorted pair: its key differs from the pair before
+#define RG_GCHG 2u                 //                             its (key, genome) differs
+
+#define RG_LOOP(i, n) \
+  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < (n); i += (uint64_t)gridDim.x * blockDim.x)
+
+#define RG_ADD(p, v) (void)__hip_atomic_fetch_add((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+#define RG_MAX(p, v) (void)__hip_atomic_fetch_max((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+
+struct RgRow {
+  long long rec, start, end, strand, label;
+};
+// One tile of RG_BLOCK rows (40 bytes each) and the row before it (the halo:
+// row tile * RG_BLOCK - 1, none for tile 0) through LDS, read as contiguous
+// 8-byte loads.  Every thread then takes its own row r and the row before it
+// p (has_prev: there is one).  Called by every thread of the block (two
+// barriers); returns whether the thread has a row.  lds: 5 * (RG_BLOCK + 1) words.
+__device__ __forceinline__ bool rg_load_tile(const long long* __restrict__ rows, uint64_t n, uint64_t tile,
+                                             long long* lds, RgRow& r, RgRow& p, bool& has_prev) {
+  const uint64_t base = tile * RG_BLOCK;                   // first row of the tile
+  const uint32_t halo = base ? 1u : 0u;
+  const uint32_t cnt = (uint32_t)(n - base < RG_BLOCK ? n - base : (uint64_t)RG_BLOCK);
+  const uint32_t nw = 5 * (cnt + halo);
+  const long long* src = rows + 5 * (base - halo);
+  __syncthreads();                                         // (the previous tile's readers are done)
+  for (uint32_t w = threadIdx.x; w < nw; w += RG_BLOCK) lds[w] = src[w];
+  __syncthreads();
+  const bool have = threadIdx.x < cnt;
+  has_prev = have && (threadIdx.x + halo) > 0;
+  if (have) {
+    const long long* q = lds + 5 * (threadIdx.x + halo);
+    r.rec = q[0]; r.start = q[1]; r.end = q[2]; r.strand = q[3]; r.label = q[4];
+    if (has_prev) { p.rec = q[-5]; p.start = q[-4]; p.end = q[-3]; p.strand = q[-2]; p.label = q[-1]; }
+  }
+  return have;
+}
+__device__ __forceinline__ ull rg_len(const RgRow& r) {
+  return r.end >= r.start ? (ull)r.end - (ull)r.start : (ull)r.start - (ull)r.end;
+}
+__device__ __forceinline__ ull rg_readlane64(ull v, int lane) {
+  const uint32_t lo = __builtin_amdgcn_readlane((int)(uint32_t)v, lane);
+  const uint32_t hi = __builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), lane);
+  return ((ull)hi << 32) | lo;
+}
+__device__ __forceinline__ ull rg_wave_sum(ull v) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ ull rg_wave_max(ull v) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) { const ull w = __shfl_xor(v, o); v = w > v ? w : v; }
+  return v;
+}
+// The lanes of a wave grouped by label (todo: the lane takes part).  A label
+// held by RG_AGG_MIN lanes or more: agg(label, mine, leader) is called by
+// every lane of the wave (it may reduce across the wave; `leader` is one of
+// the lanes that hold the label).  Returns whether the lane is left to issue
+// its own atomics.  Every lane of the wave must call it.
+template <class Agg>
+__device__ __forceinline__ bool rg_by_label(bool todo, ull lab, Agg&& agg) {
+  const int lane = threadIdx.x & 63;
+  bool own = false;
+  for (;;) {
+    const ull open = __ballot(todo);
+    if (!open) break;
+    const int lead = __ffsll(open) - 1;
+    const ull lab0 = rg_readlane64(lab, lead);
+    const bool mine = todo && lab == lab0;
+    const ull m = __ballot(mine);
+    todo = todo && !mine;
+    if (__popcll(m) < RG_AGG_MIN) {
+      own = own || mine;
+      continue;
+    }
+    agg(lab0, mine, (ull)__popcll(m), lane == lead);
+  }
+  return own;
+}
+
+// signed decimals (a host row's start and end may be negative)
+__device__ __forceinline__ uint32_t ndig_s(long long v) { return v < 0 ? 1 + ndig(0ull - (ull)v) : ndig((ull)v); }
+__device__ __forceinline__ char* put_sdec(char* o, long long v) {
+  if (v < 0) { *o++ = '-'; return put_dec(o, 0ull - (ull)v); }
+  return put_dec(o, (ull)v);
+}
+template <size_t N>
+__device__ __forceinline__ char* put_lit(char* o, const char (&s)[N]) {
+#pragma unroll
+  for (size_t i = 0; i + 1 < N; ++i) o[i] = s[i];
+  return o + (N - 1);
+}
+
+// ------------------------------------------------------------ a. scan
+// rf[i] = RG_USED | RG_HEAD of row i; out[0] = 1 + the largest used label (0: none), out[1] = used rows,
+// out[2] = skipped rows, out[3] = 1 + the largest record of a used row
+__global__ void __launch_bounds__(RG_BLOCK) k_rg_scan(const long long* __restrict__ rows, uint64_t n,
+                                                      const int* __restrict__ rec_group, uint8_t* __restrict__ rf,
+                                                      ull* __restrict__ out) {
+  __shared__ long long lds[5 * (RG_BLOCK + 1)];
+  const uint64_t ntiles = (n + RG_BLOCK - 1) / RG_BLOCK;
+  ull top = 0, used = 0, skipped = 0, toprec = 0;
+  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    RgRow r, p;
+    bool hp;
+    if (rg_load_tile(rows, n, t, lds, r, p, hp)) {
+      const bool u = r.label >= 0 && rec_group[r.rec] >= 0;
+      // the row before continues into this one: used, same record and strand
+      const bool cont = u && hp && p.rec == r.rec && p.strand == r.strand && p.label >= 0 && rec_group[p.rec] >= 0;
+      rf[t * RG_BLOCK + threadIdx.x] = (uint8_t)((u ? RG_USED : 0u) | (u && !cont ? RG_HEAD : 0u));
+      used += u;
+      skipped += !u;
+      if (u && (ull)r.label + 1 > top) top = (ull)r.label + 1;
+      if (u && (ull)r.rec + 1 > toprec) toprec = (ull)r.rec + 1;
+    }
+  }
+  top = rg_wave_max(top);
+  toprec = rg_wave_max(toprec);
+  used = rg_wave_sum(used);
+  skipped = rg_wave_sum(skipped);
+  if ((threadIdx.x & 63) == 0) {
+    if (top) RG_MAX(out, top);
+    if (used) RG_ADD(out + 1, used);
+    if (skipped) RG_ADD(out + 2, skipped);
+    if (toprec) RG_MAX(out + 3, toprec);
+  }
+}
+
+// ------------------------------------------------------------ b. steps, paths, pairs
+// the path table's columns (np entries); lo / hi / steps hold the head's start / end and the
+// tail's step index until k_rg_pathfin
+struct RgPaths {
+  long long *rec, *strand, *lo, *hi;
+  ull *steps, *first;
+  static size_t bytes(uint64_t np) { return 48 * np + 64; }
+  RgPaths(const DevBuf& b, uint64_t np) {
+    rec = b.as<long long>();
+    strand = rec + np;
+    lo = strand + np;
+    hi = lo + np;
+    steps = reinterpret_cast<ull*>(hi + np);
+    first = steps + np;
+  }
+};
+// uoff[i] / hoff[i]: the used rows / run heads before row i; rf[n] = 0
+__global__ void __launch_bounds__(RG_BLOCK) k_rg_emit(const long long* __restrict__ rows, uint64_t n,
+                                                      const int* __restrict__ rec_group,
+                                                      const uint8_t* __restrict__ rf, const ull* __restrict__ uoff,
+                                                      const ull* __restrict__ hoff, int lb,
+                                                      long long* __restrict__ step_label,
+                                                      uint8_t* __restrict__ step_flag, RgPaths P,
+                                                      long long* __restrict__ tail_start,
+                                                      long long* __restrict__ tail_end, ull* __restrict__ pkey,
+                                                      ull* __restrict__ pgen) {
+  __shared__ long long lds[5 * (RG_BLOCK + 1)];
+  const uint64_t ntiles = (n + RG_BLOCK - 1) / RG_BLOCK;
+  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    RgRow r, p;
+    bool hp;
+    if (!rg_load_tile(rows, n, t, lds, r, p, hp)) continue;
+    const uint64_t i = t * RG_BLOCK + threadIdx.x;
+    const uint32_t f = rf[i];
+    if (!(f & RG_USED)) continue;
+    const bool head = (f & RG_HEAD) != 0;
+    const uint32_t fn = rf[i + 1];                         // (rf[n] = 0)
+    const bool last = !((fn & RG_USED) && !(fn & RG_HEAD));
+    const ull s = uoff[i];
+    const ull pid = hoff[i] + (head ? 1 : 0) - 1;          // (a used row that is no head has a head before it)
+    step_label[s] = r.label;
+    step_flag[s] = (uint8_t)((head ? RG_FIRST : 0u) | (last ? RG_LAST : 0u));
+    if (head) {
+      P.rec[pid] = r.rec;
+      P.strand[pid] = r.strand;
+      P.lo[pid] = r.start;
+      P.hi[pid] = r.end;
+      P.first[pid] = s;
+    } else {
+      const ull j = s - hoff[i];                           // the used rows before i that are no heads
+      pkey[j] = ((ull)p.label << lb) | (ull)r.label;
+      pgen[j] = (ull)(uint32_t)rec_group[r.rec];
+    }
+    if (last) {
+      tail_start[pid] = r.start;
+      tail_end[pid] = r.end;
+      P.steps[pid] = s;
+    }
+  }
+}
+__global__ void k_rg_pathfin(RgPaths P, const long long* __restrict__ tail_start,
+                             const long long* __restrict__ tail_end, uint64_t np) {
+  RG_LOOP(i, np) {
+    if (tail_start[i] < P.lo[i]) P.lo[i] = tail_start[i];
+    if (tail_end[i] > P.hi[i]) P.hi[i] = tail_end[i];
+    P.steps[i] = P.steps[i] - P.first[i] + 1;
+  }
+}
+
+// ------------------------------------------------------------ c. links
+struct RgLinks {
+  long long *from, *to;
+  ull* count;
+  uint32_t* ngen;
+  static size_t bytes(uint64_t nl) { return 28 * nl + 64; }
+  RgLinks(const DevBuf& b, uint64_t nl) {
+    from = b.as<long long>();
+    to = from + nl;
+    count = reinterpret_cast<ull*>(to + nl);
+    ngen = reinterpret_cast<uint32_t*>(count + nl);
+  }
+};
+// key / gen: the pairs in (key, genome) order; lf[np] = 0
+__global__ void k_rg_lflags(const ull* __restrict__ key, const ull* __restrict__ gen, uint64_t np,
+                            uint8_t* __restrict__ lf) {
+  RG_LOOP(j, np) {
+    const bool link = j == 0 || key[j] != key[j - 1];
+    const bool gchg = link || gen[j] != gen[j - 1];
+    lf[j] = (uint8_t)((link ? RG_LINK : 0u) | (gchg ? RG_GCHG : 0u));
+  }
+}
+// lnum[j] / gsum[j]: the links / (key, genome) changes before pair j
+__global__ void k_rg_links(const ull* __restrict__ key, const uint8_t* __restrict__ lf, const ull* __restrict__ lnum,
+                           const ull* __restrict__ gsum, uint64_t np, int lb, RgLinks T, ull* __restrict__ lpos,
+                           ull* __restrict__ gpos) {
+  RG_LOOP(j, np) {
+    if (!(lf[j] & RG_LINK)) continue;
+    const ull l = lnum[j];
+    T.from[l] = (long long)(key[j] >> lb);
+    T.to[l] = (long long)(key[j] & ((1ull << lb) - 1ull));
+    lpos[l] = j;
+    gpos[l] = gsum[j];
+  }
+}
+__global__ void k_rg_linkfin(RgLinks T, const ull* __restrict__ lpos, const ull* __restrict__ gpos, uint64_t nl,
+                             ull np, ull ng) {
+  RG_LOOP(l, nl) {
+    const bool more = l + 1 < nl;
+    T.count[l] = (more ? lpos[l + 1] : np) - lpos[l];
+    T.ngen[l] = (uint32_t)((more ? gpos[l + 1] : ng) - gpos[l]);
+  }
+}
+
+// ------------------------------------------------------------ d. nodes
+struct RgNodes {
+  long long* label;
+  ull *rows, *maxlen;
+  uint32_t *nout, *nin;
+  static size_t bytes(uint64_t nn) { return 32 * nn + 64; }
+  RgNodes(const DevBuf& b, uint64_t nn) {
+    label = b.as<long long>();
+    rows = reinterpret_cast<ull*>(label + nn);
+    maxlen = rows + nn;
+    nout = reinterpret_cast<uint32_t*>(maxlen + nn);
+    nin = nout + nn;
+  }
+};
+__global__ void __launch_bounds__(RG_BLOCK) k_rg_accum(const long long* __restrict__ rows, uint64_t n,
+                                                       const uint8_t* __restrict__ rf, ull* d_rows, ull* d_max) {
+  __shared__ long long lds[5 * (RG_BLOCK + 1)];
+  const uint64_t ntiles = (n + RG_BLOCK - 1) / RG_BLOCK;
+  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
+    RgRow r, p;
+    bool hp;
+    const bool have = rg_load_tile(rows, n, t, lds, r, p, hp);
+    const bool todo = have && (rf[t * RG_BLOCK + threadIdx.x] & RG_USED);
+    const ull lab = todo ? (ull)r.label : 0ull;
+    const ull len = todo ? rg_len(r) : 0ull;
+    // every lane of the wave runs the loop (its conditions are ballots)
+    const bool own = rg_by_label(todo, lab, [&](ull lab0, bool mine, ull cnt, bool leader) {
+      const ull hi = rg_wave_max(mine ? len : 0ull);
+      if (leader) {
+        RG_ADD(d_rows + lab0, cnt);
+        RG_MAX(d_max + lab0, hi);
+      }
+    });
+    if (own) {
+      RG_ADD(d_rows + lab, 1ull);
+      RG_MAX(d_max + lab, len);
+    }
+  }
+}
+// one count per link into its two ends: d_out[from], d_in[to]
+__global__ void __launch_bounds__(RG_BLOCK) k_rg_degree(RgLinks T, uint64_t nl, uint32_t* d_out, uint32_t* d_in) {
+  // (whole blocks step together: every lane of a wave runs rg_by_label)
+  for (uint64_t base = blockIdx.x * (uint64_t)RG_BLOCK; base < nl; base += (uint64_t)gridDim.x * RG_BLOCK) {
+    const uint64_t l = base + threadIdx.x;
+    const bool todo = l < nl;
+    const ull a = todo ? (ull)T.from[l] : 0ull, b = todo ? (ull)T.to[l] : 0ull;
+    if (rg_by_label(todo, a, [&](ull lab0, bool, ull cnt, bool leader) {
+          if (leader) RG_ADD(d_out + lab0, (uint32_t)cnt);
+        }))
+      RG_ADD(d_out + a, 1u);
+    if (rg_by_label(todo, b, [&](ull lab0, bool, ull cnt, bool leader) {
+          if (leader) RG_ADD(d_in + lab0, (uint32_t)cnt);
+        }))
+      RG_ADD(d_in + b, 1u);
+  }
+}
+__global__ void k_rg_seen(const ull* __restrict__ d_rows, uint64_t L, uint8_t* __restrict__ flag) {
+  RG_LOOP(l, L) flag[l] = d_rows[l] != 0;
+}
+__global__ void k_rg_gather(RgNodes T, uint64_t nn, const ull* __restrict__ d_rows, const ull* __restrict__ d_max,
+                            const uint32_t* __restrict__ d_out, const uint32_t* __restrict__ d_in) {
+  RG_LOOP(i, nn) {
+    const uint64_t l = (uint64_t)T.label[i];
+    T.rows[i] = d_rows[l];
+    T.maxlen[i] = d_max[l];
+    T.nout[i] = d_out[l];
+    T.nin[i] = d_in[l];
+  }
+}
+
+// ------------------------------------------------------------ e. text
+#define RG_LINKS_HEADER "#from\tto\tcount\tgenomes\n"
+#define RG_GFA_HEADER "H\tVN:Z:1.0\n"
+#define RG_S1 "S\t"
+#define RG_S2 "\t*\tLN:i:"
+#define RG_L1 "L\t"
+#define RG_L2 "\t+\t"
+#define RG_L3 "\t+\t0M\tRC:i:"
+#define RG_L4 "\tgn:i:"
+#define RG_P1 "P\t"
+#define RG_P2 "\t*\n"
+#define RG_LIT(s) (sizeof(s) - 1)
+
+__global__ void k_rg_llen(RgLinks T, uint64_t nl, ull* __restrict__ len) {
+  RG_LOOP(i, nl) len[i] = ndig((ull)T.from[i]) + ndig((ull)T.to[i]) + ndig(T.count[i]) + ndig(T.ngen[i]) + 4;
+}
+__global__ void k_rg_lwrite(RgLinks T, uint64_t nl, const ull* __restrict__ off, char* __restrict__ out) {
+  RG_LOOP(i, nl) {
+    char* o = out + off[i];
+    o = put_dec(o, (ull)T.from[i]); *o++ = '\t';
+    o = put_dec(o, (ull)T.to[i]); *o++ = '\t';
+    o = put_dec(o, T.count[i]); *o++ = '\t';
+    o = put_dec(o, T.ngen[i]); *o = '\n';
+  }
+}
+// the path whose first step is s (there is one): the last p with first[p] <= s
+__device__ __forceinline__ uint64_t rg_path_of(const ull* __restrict__ first, uint64_t np, ull s) {
+  uint64_t lo = 0, hi = np;                                // first[lo] <= s < first[hi]
+  while (hi - lo > 1) {
+    const uint64_t mid = lo + (hi - lo) / 2;
+    if (first[mid] <= s) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+// items: nn S lines, nl L lines, nu path steps
+__global__ void k_rg_glen(RgNodes N, uint64_t nn, RgLinks T, uint64_t nl, const long long* __restrict__ step_label,
+                          const uint8_t* __restrict__ step_flag, uint64_t nu, RgPaths P, uint64_t np,
+                          const long long* __restrict__ name_off, ull* __restrict__ len) {
+  RG_LOOP(i, nn + nl + nu) {
+    ull v;
+    if (i < nn) {
+      v = RG_LIT(RG_S1) + ndig((ull)N.label[i]) + RG_LIT(RG_S2) + ndig(N.maxlen[i]) + 1;
+    } else if (i < nn + nl) {
+      const uint64_t l = i - nn;
+      v = RG_LIT(RG_L1) + ndig((ull)T.from[l]) + RG_LIT(RG_L2) + ndig((ull)T.to[l]) + RG_LIT(RG_L3) +
+          ndig(T.count[l]) + RG_LIT(RG_L4) + ndig(T.ngen[l]) + 1;
+    } else {
+      const uint64_t s = i - nn - nl;
+      const uint32_t f = step_flag[s];
+      v = ndig((ull)step_label[s]) + 1 + ((f & RG_LAST) ? RG_LIT(RG_P2) : 1);
+      if (f & RG_FIRST) {
+        const uint64_t p = rg_path_of(P.first, np, s);
+        const long long r = P.rec[p];
+        v += RG_LIT(RG_P1) + (ull)(name_off[r + 1] - name_off[r]) + 1 + ndig_s(P.lo[p]) + 1 + ndig_s(P.hi[p]) + 3;
+      }
+    }
+    len[i] = v;
+  }
+}
+__global__ void k_rg_gwrite(RgNodes N, uint64_t nn, RgLinks T, uint64_t nl, const long long* __restrict__ step_label,
+                            const uint8_t* __restrict__ step_flag, uint64_t nu, RgPaths P, uint64_t np,
+                            const char* __restrict__ names, const long long* __restrict__ name_off,
+                            const ull* __restrict__ off, char* __restrict__ out) {
+  RG_LOOP(i, nn + nl + nu) {
+    char* o = out + off[i];
+    if (i < nn) {
+      o = put_lit(o, RG_S1);
+      o = put_dec(o, (ull)N.label[i]);
+      o = put_lit(o, RG_S2);
+      o = put_dec(o, N.maxlen[i]);
+      *o = '\n';
+    } else if (i < nn + nl) {
+      const uint64_t l = i - nn;
+      o = put_lit(o, RG_L1);
+      o = put_dec(o, (ull)T.from[l]);
+      o = put_lit(o, RG_L2);
+      o = put_dec(o, (ull)T.to[l]);
+      o = put_lit(o, RG_L3);
+      o = put_dec(o, T.count[l]);
+      o = put_lit(o, RG_L4);
+      o = put_dec(o, T.ngen[l]);
+      *o = '\n';
+    } else {
+      const uint64_t s = i - nn - nl;
+      const uint32_t f = step_flag[s];
+      if (f & RG_FIRST) {
+        const uint64_t p = rg_path_of(P.first, np, s);
+        const long long r = P.rec[p];
+        o = put_lit(o, RG_P1);
+        for (long long b = name_off[r]; b < name_off[r + 1]; ++b) *o++ = names[b];
+        *o++ = ':';
+        o = put_sdec(o, P.lo[p]);
+        *o++ = '-';
+        o = put_sdec(o, P.hi[p]);
+        *o++ = ':';
+        *o++ = P.strand[p] == 1 ? '+' : '-';
+        *o++ = '\t';
+      }
+      o = put_dec(o, (ull)step_label[s]);
+      *o++ = '+';
+      if (f & RG_LAST) put_lit(o, RG_P2); else *o = ',';
+    }
+  }
+}
+
+#define RG_LAUNCH(kern, grid, ...)                                                       \
+  do {                                                                                   \
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(RG_BLOCK), 0, c.stream, __VA_ARGS__);      \
+    PG_HIP(hipGetLastError());                                                           \
+  } while (0)
+
+// off[0 .. n]: the flag bytes with `bit` set before each position (f[n] must be 0); returns off[n]
+struct RgBit {
+  uint32_t bit;
+  __host__ __device__ ull operator()(uint8_t f) const { return (f & bit) ? 1ull : 0ull; }
+};
+static uint64_t scan_bit(Ctx& c, const uint8_t* f, uint32_t bit, ull* off, uint64_t n) {
+  with_temp(c, [&](void* tmp, size_t& bytes) {
+    return rocprim::exclusive_scan(tmp, bytes, rocprim::make_transform_iterator(f, RgBit{bit}), off, 0ull,
+                                   (size_t)n + 1, rocprim::plus<ull>(), c.stream);
+  });
+  ull h = 0;
+  PG_HIP(hipMemcpyAsync(&h, off + n, 8, hipMemcpyDeviceToHost, c.stream));
+  c.sync();
+  return h;
+}
+
+void region_graph(Ctx& c, const int64_t* h_rows5, uint64_t n_rows, const int32_t* rec_group, uint64_t n_records,
+                  uint32_t G, uint64_t* n_nodes, uint64_t* n_links, uint64_t* n_paths, uint64_t* n_skipped) {
+  // ---- arguments (pg_freq's list): everything refused here leaves the previous result in place
+  if (!rec_group) throw Error(-22, "pg_region_graph: rec_group is NULL");
+  if (!h_rows5) {
+    if (!c.rows_ready) throw Error(-22, "pg_region_graph: no row pass (call pg_rows first, or pass rows)");
+    if (n_records != c.n_records)
+      throw Error(-22, "pg_region_graph: " + std::to_string(n_records) + " records, the context has " +
+                           std::to_string(c.n_records));
+    n_rows = c.n_rows;
+  }
+  for (uint64_t r = 0; r < n_records; ++r)
+    if (rec_group[r] < -1 || (int64_t)rec_group[r] >= (int64_t)G)
+      throw Error(-22, "pg_region_graph: rec_group[" + std::to_string(r) + "] = " + std::to_string(rec_group[r]) +
+                           " is outside [-1, " + std::to_string(G) + ")");
+  if (h_rows5)
+    for (uint64_t i = 0; i < n_rows; ++i)
+      if (h_rows5[5 * i] < 0 || (uint64_t)h_rows5[5 * i] >= n_records)
+        throw Error(-22, "pg_region_graph: row " + std::to_string(i) + " names record " +
+                             std::to_string(h_rows5[5 * i]) + " of " + std::to_string(n_records));
+  if (G == 0 && n_rows) throw Error(-22, "pg_region_graph: n_groups is 0 with rows");
+
+  const uint64_t n = n_rows;
+  const unsigned grid_rows = grid_for((n + RG_BLOCK - 1) / RG_BLOCK, 1, 8u * (unsigned)std::max(1, c.n_cu));
+  DevBuf up, grpmap, ctr, rf;
+  const long long* rows = c.rows_buf.as<long long>();
+  if (h_rows5) {
+    up.reserve(40 * (n + 1));
+    if (n) PG_HIP(hipMemcpyAsync(up.p, h_rows5, 40 * n, hipMemcpyHostToDevice, c.stream));
+    rows = up.as<long long>();
+  }
+  grpmap.reserve(4 * (n_records + 1));
+  if (n_records) PG_HIP(hipMemcpyAsync(grpmap.p, rec_group, 4 * n_records, hipMemcpyHostToDevice, c.stream));
+  const int* d_group = grpmap.as<int>();
+
+  // ---- a. the flags and the dense size, found before anything is allocated or replaced
+  ull h4[4] = {0, 0, 0, 0};
+  rf.reserve(n + 16);
+  if (n) {
+    ctr.reserve(32);
+    PG_HIP(hipMemsetAsync(ctr.p, 0, 32, c.stream));
+    PG_HIP(hipMemsetAsync(rf.as<uint8_t>() + n, 0, 1, c.stream));
+    RG_LAUNCH(k_rg_scan, grid_rows, rows, n, d_group, rf.as<uint8_t>(), ctr.as<ull>());
+    PG_HIP(hipMemcpyAsync(h4, ctr.p, 32, hipMemcpyDeviceToHost, c.stream));
+    c.sync();
+  }
+  const uint64_t L = h4[0], nu = h4[1];
+  if (L > (1ull << 31))
+    throw Error(-34, "pg_region_graph: the largest used label is " + std::to_string(L - 1) +
+                         ": the dense tables take labels below 2^31");
+  const int lb = bits_for(L ? L - 1 : 0);                  // a pair key a << lb | b has at most 62 bits
+
+  DevBuf uoff, hoff, steps, paths, tails, keyA, keyB, genA, genB, lf, lnum, gsum, lpos, links, dense, seen, labs,
+      cntb, nodes, tlen, toff, text;
+  uint64_t np = 0, npairs = 0, nl = 0, nn = 0;
+  steps.reserve(9 * nu + 64);
+  long long* step_label = steps.as<long long>();
+  uint8_t* step_flag = reinterpret_cast<uint8_t*>(step_label + nu);
+  if (nu) {
+    // ---- the step index and the run id of every row
+    uoff.reserve(8 * (n + 1));
+    hoff.reserve(8 * (n + 1));
+    const uint64_t used = scan_bit(c, rf.as<uint8_t>(), RG_USED, uoff.as<ull>(), n);
+    np = scan_bit(c, rf.as<uint8_t>(), RG_HEAD, hoff.as<ull>(), n);
+    if (used != nu || np == 0 || np > nu) throw Error(-5, "pg_region_graph: the scans disagree with the row pass");
+    npairs = nu - np;
+  }
+  paths.reserve(RgPaths::bytes(np));
+  RgPaths P(paths, np);
+  if (nu) {
+    // ---- b. steps, paths, pairs
+    tails.reserve(16 * np + 16);
+    keyA.reserve(8 * (npairs + 1));
+    genA.reserve(8 * (npairs + 1));
+    RG_LAUNCH(k_rg_emit, grid_rows, rows, n, d_group, rf.as<uint8_t>(), uoff.as<ull>(), hoff.as<ull>(), lb,
+              step_label, step_flag, P, tails.as<long long>(), tails.as<long long>() + np, keyA.as<ull>(),
+              genA.as<ull>());
+    RG_LAUNCH(k_rg_pathfin, grid_for(np, RG_BLOCK, 8192), P, tails.as<long long>(), tails.as<long long>() + np, np);
+  }
+  if (npairs) {
+    // ---- c. (key, genome) order: stable sorts by genome, then by key
+    keyB.reserve(8 * (npairs + 1));
+    genB.reserve(8 * (npairs + 1));
+    sort_pairs(c, genA.as<ull>(), genB.as<ull>(), keyA.as<ull>(), keyB.as<ull>(), npairs, bits_for(G - 1));
+    sort_pairs(c, keyB.as<ull>(), keyA.as<ull>(), genB.as<ull>(), genA.as<ull>(), npairs, 2 * lb);
+    lf.reserve(npairs + 16);
+    lnum.reserve(8 * (npairs + 1));
+    gsum.reserve(8 * (npairs + 1));
+    PG_HIP(hipMemsetAsync(lf.as<uint8_t>() + npairs, 0, 1, c.stream));
+    RG_LAUNCH(k_rg_lflags, grid_for(npairs, RG_BLOCK, 8192), keyA.as<ull>(), genA.as<ull>(), npairs,
+              lf.as<uint8_t>());
+    nl = scan_bit(c, lf.as<uint8_t>(), RG_LINK, lnum.as<ull>(), npairs);
+    const uint64_t ng = scan_bit(c, lf.as<uint8_t>(), RG_GCHG, gsum.as<ull>(), npairs);
+    links.reserve(RgLinks::bytes(nl));
+    lpos.reserve(16 * (nl + 1));
+    RgLinks T(links, nl);
+    RG_LAUNCH(k_rg_links, grid_for(npairs, RG_BLOCK, 8192), keyA.as<ull>(), lf.as<uint8_t>(), lnum.as<ull>(),
+              gsum.as<ull>(), npairs, lb, T, lpos.as<ull>(), lpos.as<ull>() + nl);
+    RG_LAUNCH(k_rg_linkfin, grid_for(nl, RG_BLOCK, 8192), T, lpos.as<ull>(), lpos.as<ull>() + nl, nl, (ull)npairs,
+              (ull)ng);
+  } else {
+    links.reserve(RgLinks::bytes(0));
+  }
+  RgLinks T(links, nl);
+  if (L) {
+    // ---- d. dense per-label arrays: rows, max length (8 bytes), links out, links in (4 bytes)
+    dense.reserve(24 * (size_t)L);
+    ull *d_rows = dense.as<ull>(), *d_max = d_rows + L;
+    uint32_t *d_out = reinterpret_cast<uint32_t*>(d_max + L), *d_in = d_out + L;
+    PG_HIP(hipMemsetAsync(dense.p, 0, 24 * (size_t)L, c.stream));
+    RG_LAUNCH(k_rg_accum, grid_rows, rows, n, rf.as<uint8_t>(), d_rows, d_max);
+    if (nl) RG_LAUNCH(k_rg_degree, grid_for(nl, RG_BLOCK, 1024), T, nl, d_out, d_in);
+    seen.reserve(L + 16);
+    RG_LAUNCH(k_rg_seen, grid_for(L, RG_BLOCK, 8192), d_rows, L, seen.as<uint8_t>());
+    labs.reserve(8 * (L + 1));
+    cntb.reserve(16);
+    with_temp(c, [&](void* tmp, size_t& bytes) {
+      return rocprim::select(tmp, bytes, rocprim::counting_iterator<long long>(0), seen.as<uint8_t>(),
+                             labs.as<long long>(), cntb.as<ull>(), (size_t)L, c.stream);
+    });
+    ull h = 0;
+    PG_HIP(hipMemcpyAsync(&h, cntb.p, 8, hipMemcpyDeviceToHost, c.stream));
+    c.sync();
+    nn = h;
+    nodes.reserve(RgNodes::bytes(nn));
+    RgNodes N(nodes, nn);
+    PG_HIP(hipMemcpyAsync(N.label, labs.p, 8 * nn, hipMemcpyDeviceToDevice, c.stream));
+    RG_LAUNCH(k_rg_gather, grid_for(nn, RG_BLOCK, 8192), N, nn, d_rows, d_max, d_out, d_in);
+  } else {
+    nodes.reserve(RgNodes::bytes(0));
+  }
+  // ---- e. the links text: the header, then one line per link
+  const size_t hdr = RG_LIT(RG_LINKS_HEADER);
+  uint64_t body = 0;
+  if (nl) {
+    tlen.reserve(8 * (nl + 1));
+    toff.reserve(8 * (nl + 1));
+    RG_LAUNCH(k_rg_llen, grid_for(nl, RG_BLOCK, 8192), T, nl, tlen.as<ull>());
+    body = excl_scan_total(c, tlen.as<ull>(), toff.as<ull>(), nl);
+  }
+  text.reserve(hdr + body + 16);
+  PG_HIP(hipMemcpyAsync(text.p, RG_LINKS_HEADER, hdr, hipMemcpyHostToDevice, c.stream));
+  if (nl) RG_LAUNCH(k_rg_lwrite, grid_for(nl, RG_BLOCK, 8192), T, nl, toff.as<ull>(), text.as<char>() + hdr);
+  c.sync();
+  // ---- the new result replaces the previous one
+  c.rg_nodes.swap(nodes);
+  c.rg_links.swap(links);
+  c.rg_paths.swap(paths);
+  c.rg_steps.swap(steps);
+  c.rg_text.swap(text);
+  c.rg_nn = nn;
+  c.rg_nl = nl;
+  c.rg_np = np;
+  c.rg_nu = nu;
+  c.rg_total = hdr + body;
+  c.rg_names = h_rows5 ? h4[3] : c.n_records;
+  c.rg_ready = true;
+  if (n_nodes) *n_nodes = nn;
+  if (n_links) *n_links = nl;
+  if (n_paths) *n_paths = np;
+  if (n_skipped) *n_skipped = h4[2];
+}
+
+static void rg_need(const Ctx& c, const char* what) {
+  if (!c.rg_ready) throw Error(-22, std::string(what) + ": no region graph (call pg_region_graph first)");
+}
+static void rg_get(Ctx& c, void* dst, const void* src, size_t bytes) {
+  if (dst && bytes) PG_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c.stream));
+}
+
+void region_nodes(Ctx& c, int64_t* label, uint64_t* n_rows, uint64_t* max_len, uint32_t* n_out, uint32_t* n_in,
+                  uint64_t cap) {
+  rg_need(c, "pg_region_nodes");
+  const uint64_t nn = c.rg_nn;
+  if (cap < nn) throw Error(-34, "pg_region_nodes: buffer too small");
+  if (!nn) return;
+  RgNodes N(c.rg_nodes, nn);
+  rg_get(c, label, N.label, 8 * nn);
+  rg_get(c, n_rows, N.rows, 8 * nn);
+  rg_get(c, max_len, N.maxlen, 8 * nn);
+  rg_get(c, n_out, N.nout, 4 * nn);
+  rg_get(c, n_in, N.nin, 4 * nn);
+  c.sync();
+}
+
+void region_links(Ctx& c, int64_t* from, int64_t* to, uint64_t* count, uint32_t* n_genomes, uint64_t cap) {
+  rg_need(c, "pg_region_links");
+  const uint64_t nl = c.rg_nl;
+  if (cap < nl) throw Error(-34, "pg_region_links: buffer too small");
+  if (!nl) return;
+  RgLinks T(c.rg_links, nl);
+  rg_get(c, from, T.from, 8 * nl);
+  rg_get(c, to, T.to, 8 * nl);
+  rg_get(c, count, T.count, 8 * nl);
+  rg_get(c, n_genomes, T.ngen, 4 * nl);
+  c.sync();
+}
+
+void region_paths(Ctx& c, int64_t* record, int64_t* strand, int64_t* lo, int64_t* hi, uint64_t* n_steps,
+                  uint64_t cap) {
+  rg_need(c, "pg_region_paths");
+  const uint64_t np = c.rg_np;
+  if (cap < np) throw Error(-34, "pg_region_paths: buffer too small");
+  if (!np) return;
+  RgPaths P(c.rg_paths, np);
+  rg_get(c, record, P.rec, 8 * np);
+  rg_get(c, strand, P.strand, 8 * np);
+  rg_get(c, lo, P.lo, 8 * np);
+  rg_get(c, hi, P.hi, 8 * np);
+  rg_get(c, n_steps, P.steps, 8 * np);
+  c.sync();
+}
+
+// the links text of the last region_graph: its size (out null, fd < 0), copied into out, or written to fd
+uint64_t format_region_links(Ctx& c, char* out, uint64_t cap, int fd) {
+  rg_need(c, fd >= 0 ? "pg_region_links_format_fd" : "pg_region_links_format");
+  if (!out && fd < 0) return c.rg_total;
+  if (out && cap < c.rg_total) throw Error(-34, "pg_region_links_format: buffer too small");
+  if (out) {
+    PG_HIP(hipMemcpyAsync(out, c.rg_text.p, c.rg_total, hipMemcpyDeviceToHost, c.stream));
+    c.sync();
+  } else {
+    text_to_fd(c, c.rg_text.as<uint8_t>(), c.rg_total, fd, "pg_region_links_format_fd");
+  }
+  return c.rg_total;
+}
+
+// the GFA text of the last region_graph with this call's record names (names[name_off[r] ..
+// name_off[r+1]) is record r's): its size (out null, fd < 0), copied into out, or written to fd
+uint64_t format_region_gfa(Ctx& c, const char* names, const int64_t* name_off, uint64_t n_names, char* out,
+                           uint64_t cap, int fd) {
+  const char* what = fd >= 0 ? "pg_region_gfa_fd" : "pg_region_gfa";
+  rg_need(c, what);
+  if (!name_off) throw Error(-22, std::string(what) + ": name_off is NULL");
+  if (n_names < c.rg_names)
+    throw Error(-22, std::string(what) + ": " + std::to_string(n_names) + " names, the paths need " +
+                         std::to_string(c.rg_names));
+  for (uint64_t r = 0; r < n_names; ++r)
+    if (name_off[r] < 0 || name_off[r + 1] < name_off[r])
+      throw Error(-22, std::string(what) + ": name_off is not ascending from 0 up");
+  const uint64_t nbytes = (uint64_t)name_off[n_names];
+  if (nbytes && !names) throw Error(-22, std::string(what) + ": names is NULL");
+  const uint64_t nn = c.rg_nn, nl = c.rg_nl, nu = c.rg_nu, np = c.rg_np, items = nn + nl + nu;
+  const size_t hdr = RG_LIT(RG_GFA_HEADER);
+  DevBuf nm, tlen, toff, text;
+  uint64_t body = 0;
+  RgNodes N(c.rg_nodes, nn);
+  RgLinks T(c.rg_links, nl);
+  RgPaths P(c.rg_paths, np);
+  const long long* step_label = c.rg_steps.as<long long>();
+  const uint8_t* step_flag = reinterpret_cast<const uint8_t*>(step_label + nu);
+  nm.reserve(8 * (n_names + 1) + nbytes + 16);
+  long long* d_off = nm.as<long long>();
+  char* d_names = reinterpret_cast<char*>(d_off + n_names + 1);
+  if (items) {
+    PG_HIP(hipMemcpyAsync(d_off, name_off, 8 * (n_names + 1), hipMemcpyHostToDevice, c.stream));
+    if (nbytes) PG_HIP(hipMemcpyAsync(d_names, names, nbytes, hipMemcpyHostToDevice, c.stream));
+    tlen.reserve(8 * (items + 1));
+    toff.reserve(8 * (items + 1));
+    RG_LAUNCH(k_rg_glen, grid_for(items, RG_BLOCK, 8192), N, nn, T, nl, step_label, step_flag, nu, P, np, d_off,
+              tlen.as<ull>());
+    body = excl_scan_total(c, tlen.as<ull>(), toff.as<ull>(), items);
+  }
+  const uint64_t total = hdr + body;
+  if (!out && fd < 0) return total;
+  if (out && cap < total) throw Error(-34, std::string(what) + ": buffer too small");
+  text.reserve(total + 16);
+  PG_HIP(hipMemcpyAsync(text.p, RG_GFA_HEADER, hdr, hipMemcpyHostToDevice, c.stream));
+  if (items)
+    RG_LAUNCH(k_rg_gwrite, grid_for(items, RG_BLOCK, 8192), N, nn, T, nl, step_label, step_flag, nu, P, np, d_names,
+              d_off, toff.as<ull>(), text.as<char>() + hdr);
+  if (out) PG_HIP(hipMemcpyAsync(out, text.p, total, hipMemcpyDeviceToHost, c.stream));
+  c.sync();
+  if (!out) text_to_fd(c, text.as<uint8_t>(), total, fd, what);
+  return total;
+}
+
+}  // namespace pg

@@ -826,6 +826,34 @@ def write_compare_files(prefix: str, names, shared, orders, pan, core) -> None:
     whole("_fr_compare.npz", lambda f: np.savez(f, genomes=gn, shared=s, orders=o, pan=pan, core=core))
 
 
+REGION_COLS = (("labels", np.int64), ("rows", np.uint64), ("max_len", np.uint64), ("n_out", np.uint32),
+               ("n_in", np.uint32), ("link_from", np.int64), ("link_to", np.int64), ("link_count", np.uint64),
+               ("link_genomes", np.uint32), ("path_record", np.int64), ("path_strand", np.int64),
+               ("path_lo", np.int64), ("path_hi", np.int64), ("path_steps", np.uint64))
+
+
+def write_region_files(prefix: str, write_links, write_gfa, table: dict, genome_names) -> None:
+    """The four `-l` files of `prefix` (the input's path): `_fr_links.tsv` and
+    `_fr_graph.gfa` (write_links(file) / write_gfa(file) write the texts),
+    `_fr_nodes.tsv` from the table's node columns and `_fr_graph.npz` (every
+    column of REGION_COLS and the genome names); each is written to `.tmp`
+    and renamed when whole."""
+    def whole(suffix, fill):
+        fn = prefix + suffix
+        with open(fn + ".tmp", "wb") as f:
+            fill(f)
+        os.replace(fn + ".tmp", fn)
+    whole("_fr_links.tsv", write_links)
+    cols = [np.asarray(table[k]).tolist() for k in ("labels", "rows", "max_len", "n_out", "n_in")]
+    whole("_fr_nodes.tsv", lambda f: f.write(("#label\trows\tmax\tout\tin\n" + "".join(
+        "%d\t%d\t%d\t%d\t%d\n" % x for x in zip(*cols))).encode()))
+    whole("_fr_graph.gfa", write_gfa)
+    arrays = {k: np.ascontiguousarray(table[k], dtype=t).reshape(-1) for k, t in REGION_COLS}
+    arrays["genomes"] = (np.array([bytes(x) for x in genome_names], dtype=np.bytes_) if genome_names
+                         else np.zeros(0, "S1"))
+    whole("_fr_graph.npz", lambda f: np.savez(f, **arrays))
+
+
 def seqid(name: bytes) -> bytes:
     """A record's id: its header without '>' up to the first whitespace."""
     p = bytes(name).split(None, 1)

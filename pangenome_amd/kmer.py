@@ -9,7 +9,7 @@ runs in libpangenome_hip.so on an MI355X (pangenome_amd/csrc).  Mirrors:
   dbg2rdbg     :1313-1321                rdBG (K5 degree scan + compaction)
   seq2graph    :1853-1951                edges -> .xyz -> mcl -> labels -> rows
   dump / load_on_disk  :243-335         `<in>_db.npz` (oakht slot layout)
-  entry_point  :1971-2146                CLI (-i -k -n -c -r -d -R -D; ours: -a -w -g -p)
+  entry_point  :1971-2146                CLI (-i -k -n -c -r -d -R -D; ours: -a -w -g -p -l)
 
 Usage:  python -m pangenome_amd -i genomes.fa -k 27 > result.tab
 """
@@ -257,7 +257,7 @@ def rdbg_edges(g: DeviceGraph, Ns, chunk, rc, brkpt="", keep_on_device=False):
 
 def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_dict=None, saved=None,
               hashfunc=None, jit=True, chunk=2 ** 33, rc=False, cluster=True, out=None, min_weight=1, groups=None,
-              orders=0):
+              orders=0, links=False):
     """:1853-1951: edge weights -> `<qry>_rdbg_weight.xyz` -> mcl (or reuse)
     -> label dictionary -> print the region rows.  The edges, the label
     table, the rows and both texts are made on the device; the host writes
@@ -269,7 +269,9 @@ def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_
     they lie on the device (pg_freq) and the four `<qry>_fr_*` files written;
     nothing more is printed.  orders (-p, with groups): the genomes are then
     compared on the device table (pg_freq_compare) over that many genome
-    orders and four more `<qry>_fr_*` files written."""
+    orders and four more `<qry>_fr_*` files written.  links (-l, with groups):
+    the region graph of the device rows (pg_region_graph) is made with the
+    same genomes and its four `<qry>_fr_*` files written."""
     out = out or sys.stdout
     g = rdbg_dict
     res = rdbg_edges(g, Ns, chunk, rc, brkpt=brkpt, keep_on_device=True)
@@ -320,6 +322,8 @@ def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_
         gnames = write_freq(g, qry, names, flags, groups)
         if orders:
             write_compare(g, qry, gnames, int(orders))
+        if links:
+            write_region(g, qry, names, flags, groups)
     gen = g.ctx.label_gen
     return LabelTable(loader=lambda: g.ctx.labels(gen))           # (raises once a later label pass replaced it)
 
@@ -364,6 +368,28 @@ def write_compare(g, qry, gnames, n_orders):
     host.write_compare_files(qry, gnames, g.ctx.freq_shared(), orders, pan, core)
 
 
+def write_region(g, qry, names, flags, groups):
+    """-l: the region graph of the row pass just run (pg_region_graph on the
+    device rows, write_freq's genomes) as `<qry>_fr_links.tsv` and
+    `_fr_graph.gfa` (the device texts; a path is named by its record's seqid),
+    `_fr_nodes.tsv` and `_fr_graph.npz`."""
+    rec_group, gnames = host.assign_groups(names, flags, groups)
+    g.ctx.region_graph(rec_group, len(gnames))
+    table = g.ctx.region_nodes()
+    table.update(g.ctx.region_links())
+    table.update(g.ctx.region_paths())
+    ids = [host.seqid(x) for x in names]
+
+    def links(f):
+        f.flush()
+        g.ctx.region_links_write(f.fileno())
+
+    def gfa(f):
+        f.flush()
+        g.ctx.region_gfa_write(ids, f.fileno())
+    host.write_region_files(qry, links, gfa, table, gnames)
+
+
 def _fileno(out):
     """The descriptor under a text stream's binary buffer (stdout, a file),
     or None (a stand-in with no descriptor)."""
@@ -385,6 +411,8 @@ def manual_print(out=None):
                  "      seqid<TAB>genome lines; writes <in>_fr_freq.tsv, _fr_spectrum.tsv, _fr_genomes.tsv, _fr_presence.npz",
                  "  -p: with -g, compare the genomes over this many genome orders (0: off). writes <in>_fr_shared.tsv,",
                  "      _fr_jaccard.tsv (pairs), _fr_curve.tsv (pan and core genome growth), _fr_compare.npz",
+                 "  -l: with -g, the graph of the regions along the genomes. 0 (off) or 1; single process only. writes",
+                 "      <in>_fr_links.tsv, _fr_nodes.tsv, _fr_graph.gfa (GFA 1, the genomes as paths), _fr_graph.npz",
                  "  -c: complementary reverse sequence. 00,01,10,11",
                  "  -a: clustering of the rdBG. mcl (run or reuse mcl) or cc (built-in connected components)",
                  "  -w: with -a cc, drop edges lighter than this weight. default 1"):
@@ -394,7 +422,7 @@ def manual_print(out=None):
 def parse_args(argv):
     """:1983-1997 — same flag handling, including `-k27` and skipped unknowns."""
     args = {"-i": "", "-k": "50", "-n": "2**63", "-r": "", "-d": "", "-R": "", "-D": "", "-c": "2", "-a": "mcl",
-            "-w": "1", "-g": "", "-p": "0"}
+            "-w": "1", "-g": "", "-p": "0", "-l": "0"}
     N = len(argv)
     for i in range(1, N):
         k = argv[i]
@@ -415,13 +443,21 @@ def compare_orders_arg(args):
     return None if p < 0 or (p and not args["-g"]) else p
 
 
+def links_arg(args):
+    """-l's value: False (0) or True (1), or None for a value that is refused
+    - anything else, or 1 without -g."""
+    if args["-l"] not in ("0", "1"):
+        return None
+    return None if args["-l"] == "1" and not args["-g"] else args["-l"] == "1"
+
+
 def entry_point(argv, out=None, device=0):
     out = out or sys.stdout
     args = parse_args(argv)
     qry, kmer, Ns = args["-i"], int(args["-k"]), host.eval_number(args["-n"])
     bkt, dbs, rbk, rc, rdb = args["-r"], args["-d"], args["-R"], int(args["-c"]), args["-D"]
-    n_orders = compare_orders_arg(args)
-    if not qry or args["-a"] not in ("mcl", "cc") or n_orders is None:
+    n_orders, links = compare_orders_arg(args), links_arg(args)
+    if not qry or args["-a"] not in ("mcl", "cc") or n_orders is None or links is None:
         manual_print(out)
         raise SystemExit()
     clu = dict(cluster="cc", min_weight=int(args["-w"])) if args["-a"] == "cc" else {}
@@ -430,6 +466,8 @@ def entry_point(argv, out=None, device=0):
         clu["groups"] = grp
     if n_orders:
         clu["orders"] = n_orders
+    if links:
+        clu["links"] = True
     # a group file is checked against the records before anything is built
     chk = (lambda g: check_groups(g, Ns, grp)) if grp and grp != "record" else None
     chunk = 2 ** 33
