@@ -505,6 +505,72 @@ int pg_region_gfa(pg_ctx* ctx, const char* names, const int64_t* name_off, uint6
 int pg_region_gfa_fd(pg_ctx* ctx, const char* names, const int64_t* name_off, uint64_t n_names, int fd,
                      uint64_t* n_bytes);
 
+/* ---- region sequences: what a region is - one representative sequence per
+ *      label, decoded on the device from the parse's packed base stream (the
+ *      reference's `recover(path, dbg)` is a stub, kmer_numba.py:1953-1955).
+ *      The result depends on the input alone, whatever the schedule.
+ * Input: exactly pg_region_graph's rows, rec_group and rule for a used row;
+ * the others are counted in *n_skipped (every count pointer may be NULL).  In
+ * both forms n_records must equal the context's record count: the bases come
+ * from the context's parse.
+ * Representative of a label: its used row with the largest |end - start| (the
+ * max_len of pg_region_nodes); among equals the first in list order.
+ * Sequence: with lo = min(start, end) and hi = max(start, end), F is bases
+ * [lo, hi) of the record's compacted sequence (the coordinates the rows are
+ * printed in), one letter per base by its class: A, C, G, T; N, '$' and every
+ * other byte give N (the parse has already folded case and the IUPAC codes:
+ * no lower case and no code but N comes back).  strand == 1: F; otherwise the
+ * reverse complement of F (A<->T, C<->G, N->N) - the walk's orientation, so a
+ * GFA step <label>+ is consistent on both strands.
+ * Table: one entry per label with a used row, labels ascending: label; row,
+ * the representative's index in the list; record, start, end, strand as the
+ * row carries them; len = hi - lo; gc, its C or G letters; amb, its N letters;
+ * offset, the exclusive prefix sum of len.  The bases are the sequences one
+ * after another in table order with no separators, n_bases = the sum of len.
+ * PG_EINVAL, before any result is replaced: pg_region_graph's whole list; a
+ * context without a parse; a used row with lo < 0 or hi > the record's length
+ * (found by a device reduction before anything is allocated).  L = 1 + the
+ * largest used label > 2^31 is PG_ERANGE (the dense arrays take 16 x L device
+ * bytes while the call runs); an allocation failure is PG_ENOMEM.  In every
+ * refusal the previous result stays.
+ * The result is a copy: it stays until the next successful pg_region_seqs; a
+ * later parse or build does not touch it; pg_freq, pg_freq_compare and
+ * pg_region_graph neither read nor drop it, nor it theirs. */
+int pg_region_seqs(pg_ctx* ctx, const int64_t* rows5, uint64_t n_rows, const int32_t* rec_group,
+                   uint64_t n_records, uint32_t n_groups, uint64_t* n_regions, uint64_t* n_bases,
+                   uint64_t* n_skipped);
+/* The table and the bases of the last pg_region_seqs; any output pointer may
+ * be NULL; cap (entries, bytes) below the size is PG_ERANGE.  out == NULL:
+ * only *n_bytes is set.  These and the four text calls below: PG_EINVAL
+ * before any pg_region_seqs. */
+int pg_region_seqs_table(pg_ctx* ctx, int64_t* label, int64_t* row, int64_t* record, int64_t* start, int64_t* end,
+                         int64_t* strand, uint64_t* len, uint64_t* gc, uint64_t* amb, uint64_t* offset,
+                         uint64_t cap);
+int pg_region_seqs_bases(pg_ctx* ctx, uint8_t* out, uint64_t cap, uint64_t* n_bytes);
+/* The decoder kernel of the last pg_region_seqs: its time in ms (HIP events on
+ * the context's stream; 0 with no bases) and the 16-letter chunks it wrote
+ * (every sequence's length rounded up to 16, over 16).  Either may be NULL. */
+int pg_region_seqs_time(pg_ctx* ctx, double* ms_decode, uint64_t* n_chunks);
+/* The sequences as FASTA, formatted on the device by every call with its own
+ * names (as pg_region_gfa takes them, copied verbatim), per entry
+ *   ><label> <name>:<lo>-<hi>:<+|-> len=<len>\n<sequence>\n
+ * the sign being + iff the strand equals 1 and the sequence on one line; no
+ * entries: an empty text.  n_names, name_off, out, cap and the _fd form: as
+ * pg_region_gfa and pg_region_gfa_fd. */
+int pg_region_fasta(pg_ctx* ctx, const char* names, const int64_t* name_off, uint64_t n_names, char* out,
+                    uint64_t cap, uint64_t* n_bytes);
+int pg_region_fasta_fd(pg_ctx* ctx, const char* names, const int64_t* name_off, uint64_t n_names, int fd,
+                       uint64_t* n_bytes);
+/* pg_region_gfa's text and arguments, except that every S line carries its
+ * sequence: S\t<label>\t<sequence>\tLN:i:<max_len>\n.  It needs both a region
+ * graph and region sequences, of the same rows and groups: PG_EINVAL unless
+ * the two tables have the same labels and len == max_len for every one
+ * (checked on the device). */
+int pg_region_gfa_seq(pg_ctx* ctx, const char* names, const int64_t* name_off, uint64_t n_names, char* out,
+                      uint64_t cap, uint64_t* n_bytes);
+int pg_region_gfa_seq_fd(pg_ctx* ctx, const char* names, const int64_t* name_off, uint64_t n_names, int fd,
+                         uint64_t* n_bytes);
+
 /* ---- text output (host only; no context).  The reference formats these in
  *      Python loops (kmer_numba.py:1893-1904, :1946-1949).
  * pg_format_xyz: "%d_%d\t%d_%d\t%d\n" per edge (tuples as unsigned).

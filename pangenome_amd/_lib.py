@@ -117,6 +117,14 @@ SIGNATURES = {
     "pg_region_links_format_fd": (C.c_int, [_P, C.c_int, _U64P]),
     "pg_region_gfa": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint64, _U64P]),
     "pg_region_gfa_fd": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, _U64P]),
+    "pg_region_seqs": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, C.c_uint32, _U64P, _U64P, _U64P]),
+    "pg_region_seqs_table": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_uint64]),
+    "pg_region_seqs_bases": (C.c_int, [_P, _P, C.c_uint64, _U64P]),
+    "pg_region_seqs_time": (C.c_int, [_P, C.POINTER(C.c_double), _U64P]),
+    "pg_region_fasta": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint64, _U64P]),
+    "pg_region_fasta_fd": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, _U64P]),
+    "pg_region_gfa_seq": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint64, _U64P]),
+    "pg_region_gfa_seq_fd": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, _U64P]),
     "pg_rows_format": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint64, _U64P]),
     "pg_rows_format_fd": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, _U64P]),
     "pg_get_stats": (C.c_int, [_P, _SP]),
@@ -793,6 +801,91 @@ class Context:
         check(self.lib.pg_region_gfa_fd(self.h, ptr(nb), ptr(off), len(names), int(fd), C.byref(n)),
               "pg_region_gfa_fd")
         return n.value
+
+    # ---------------------------------------------------- region sequences
+    def region_seqs(self, rec_group, n_groups: int, rows=None):
+        """One representative sequence per label (pg_region_seqs) of the last
+        row pass where it lies on the device (rows None) or of host rows
+        [n, 5], decoded from the context's parse; rec_group as region_graph()
+        takes it.  Returns (n_regions, n_bases, n_skipped); the result stays
+        on the device (region_seqs_table / region_seqs_bases /
+        region_fasta_text / region_gfa_seq_text and their _write forms)."""
+        grp = np.ascontiguousarray(rec_group, dtype=np.int32).reshape(-1)
+        n_records = grp.shape[0]
+        if not n_records:
+            grp = np.full(1, -1, np.int32)           # (never NULL: an empty array's pointer may be)
+        r5, n_rows = None, 0
+        if rows is not None:
+            r5 = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1, 5)
+            n_rows = r5.shape[0]
+            if not n_rows:
+                r5 = np.zeros((1, 5), np.int64)      # (NULL would mean the device rows)
+        nr, nb, ns = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        check(self.lib.pg_region_seqs(self.h, ptr(r5), n_rows, ptr(grp), n_records, int(n_groups),
+                                      C.byref(nr), C.byref(nb), C.byref(ns)), "pg_region_seqs")
+        self.n_region_seqs = nr.value
+        return nr.value, nb.value, ns.value
+
+    def region_seqs_table(self) -> dict:
+        """The table of the last region_seqs(), labels ascending: label, row,
+        record, start, end, strand (int64), len, gc, amb, offset (uint64)
+        (pg_region_seqs_table)."""
+        n = getattr(self, "n_region_seqs", 0)
+        t = {k: np.empty(n, np.int64) for k in ("label", "row", "record", "start", "end", "strand")}
+        t.update({k: np.empty(n, np.uint64) for k in ("len", "gc", "amb", "offset")})
+        check(self.lib.pg_region_seqs_table(self.h, *[ptr(a) for a in t.values()], n), "pg_region_seqs_table")
+        return t
+
+    def region_seqs_bases(self) -> bytes:
+        """The sequences one after another in table order, no separators
+        (pg_region_seqs_bases)."""
+        n = C.c_uint64()
+        check(self.lib.pg_region_seqs_bases(self.h, None, 0, C.byref(n)), "pg_region_seqs_bases")
+        buf = np.empty(max(n.value, 1), np.uint8)
+        check(self.lib.pg_region_seqs_bases(self.h, ptr(buf), buf.shape[0], C.byref(n)), "pg_region_seqs_bases")
+        return buf[:n.value].tobytes()
+
+    def region_seqs_time(self):
+        """(ms, chunks): the decoder kernel's time in the last region_seqs()
+        and the 16-letter chunks it wrote (pg_region_seqs_time)."""
+        ms, n = C.c_double(), C.c_uint64()
+        check(self.lib.pg_region_seqs_time(self.h, C.byref(ms), C.byref(n)), "pg_region_seqs_time")
+        return ms.value, n.value
+
+    def _names_text(self, fn, what, names) -> bytes:
+        nb, off = _names_blob(names)
+        n = C.c_uint64()
+        check(fn(self.h, ptr(nb), ptr(off), len(names), None, 0, C.byref(n)), what)
+        buf = np.empty(max(n.value, 1), np.uint8)
+        check(fn(self.h, ptr(nb), ptr(off), len(names), ptr(buf), buf.shape[0], C.byref(n)), what)
+        return buf[:n.value].tobytes()
+
+    def _names_write(self, fn, what, names, fd) -> int:
+        nb, off = _names_blob(names)
+        n = C.c_uint64()
+        check(fn(self.h, ptr(nb), ptr(off), len(names), int(fd), C.byref(n)), what)
+        return n.value
+
+    def region_fasta_text(self, names: list) -> bytes:
+        """The sequences as FASTA, formatted on the device (pg_region_fasta);
+        names[r] = record r's name in the header lines."""
+        return self._names_text(self.lib.pg_region_fasta, "pg_region_fasta", names)
+
+    def region_fasta_write(self, names: list, fd: int) -> int:
+        """region_fasta_text(names) written straight to descriptor fd at its
+        position (pg_region_fasta_fd); flush any buffered writer on fd first."""
+        return self._names_write(self.lib.pg_region_fasta_fd, "pg_region_fasta_fd", names, fd)
+
+    def region_gfa_seq_text(self, names: list) -> bytes:
+        """region_gfa_text(names) with every S line carrying its sequence
+        (pg_region_gfa_seq): needs region_graph() and region_seqs() of the
+        same rows and groups."""
+        return self._names_text(self.lib.pg_region_gfa_seq, "pg_region_gfa_seq", names)
+
+    def region_gfa_seq_write(self, names: list, fd: int) -> int:
+        """region_gfa_seq_text(names) written straight to descriptor fd at its
+        position (pg_region_gfa_seq_fd); flush any buffered writer on fd first."""
+        return self._names_write(self.lib.pg_region_gfa_seq_fd, "pg_region_gfa_seq_fd", names, fd)
 
     def rows_export(self, n: int):
         """The [n, 5] rows of the last rows_count() (pg_rows_export)."""

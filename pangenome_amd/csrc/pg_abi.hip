@@ -96,7 +96,7 @@ void pg_destroy(pg_ctx* x) {
                         &c.edge_out, &c.edge_exp, &c.lab_tab, &c.lab_list, &c.rows_buf, &c.text_len, &c.text_off,
                         &c.text_buf, &c.text_names, &c.clu_text, &c.fr_tab, &c.fr_spec, &c.fr_grp, &c.fr_text,
                         &c.cmp_shared, &c.cmp_curve, &c.rg_nodes, &c.rg_links, &c.rg_paths, &c.rg_steps, &c.rg_text,
-                        &c.preload,
+                        &c.rs_tab, &c.rs_blob, &c.preload,
                         &c.dump_cnt};
   for (auto* b : bufs) b->release();
   pg::pool_destroy(c);
@@ -109,6 +109,7 @@ void pg_destroy(pg_ctx* x) {
   c.t0.destroy();
   c.t1.destroy();
   c.t6.destroy();
+  c.t_rs.destroy();
   for (auto& e : c.ev)
     if (e) (void)hipEventDestroy(e);
   for (auto e : c.cev)
@@ -861,6 +862,78 @@ int pg_region_gfa_fd(pg_ctx* x, const char* names, const int64_t* name_off, uint
     if (!x || !n_bytes || fd < 0) throw pg::Error(PG_EINVAL, "pg_region_gfa_fd: bad arguments");
     PG_HIP(hipSetDevice(x->c.device));
     *n_bytes = pg::format_region_gfa(x->c, names, name_off, n_names, nullptr, 0, fd);
+  });
+}
+
+int pg_region_seqs(pg_ctx* x, const int64_t* rows5, uint64_t n_rows, const int32_t* rec_group, uint64_t n_records,
+                   uint32_t n_groups, uint64_t* n_regions, uint64_t* n_bases, uint64_t* n_skipped) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_region_seqs: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::region_seqs(x->c, rows5, n_rows, rec_group, n_records, n_groups, n_regions, n_bases, n_skipped);
+  });
+}
+
+int pg_region_seqs_table(pg_ctx* x, int64_t* label, int64_t* row, int64_t* record, int64_t* start, int64_t* end,
+                         int64_t* strand, uint64_t* len, uint64_t* gc, uint64_t* amb, uint64_t* offset,
+                         uint64_t cap) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_region_seqs_table: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::region_seqs_table(x->c, label, row, record, start, end, strand, len, gc, amb, offset, cap);
+  });
+}
+
+int pg_region_seqs_bases(pg_ctx* x, uint8_t* out, uint64_t cap, uint64_t* n_bytes) {
+  return guard([&] {
+    if (!x || !n_bytes) throw pg::Error(PG_EINVAL, "pg_region_seqs_bases: bad arguments");
+    PG_HIP(hipSetDevice(x->c.device));
+    *n_bytes = pg::region_seqs_bases(x->c, out, cap);
+  });
+}
+
+int pg_region_seqs_time(pg_ctx* x, double* ms_decode, uint64_t* n_chunks) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_region_seqs_time: ctx is NULL");
+    if (!x->c.rs_ready) throw pg::Error(PG_EINVAL, "pg_region_seqs_time: no region sequences (call pg_region_seqs first)");
+    if (ms_decode) *ms_decode = x->c.ms_rs_decode;
+    if (n_chunks) *n_chunks = x->c.rs_chunks;
+  });
+}
+
+int pg_region_fasta(pg_ctx* x, const char* names, const int64_t* name_off, uint64_t n_names, char* out, uint64_t cap,
+                    uint64_t* n_bytes) {
+  return guard([&] {
+    if (!x || !n_bytes) throw pg::Error(PG_EINVAL, "pg_region_fasta: bad arguments");
+    PG_HIP(hipSetDevice(x->c.device));
+    *n_bytes = pg::format_region_fasta(x->c, names, name_off, n_names, out, cap);
+  });
+}
+
+int pg_region_fasta_fd(pg_ctx* x, const char* names, const int64_t* name_off, uint64_t n_names, int fd,
+                       uint64_t* n_bytes) {
+  return guard([&] {
+    if (!x || !n_bytes || fd < 0) throw pg::Error(PG_EINVAL, "pg_region_fasta_fd: bad arguments");
+    PG_HIP(hipSetDevice(x->c.device));
+    *n_bytes = pg::format_region_fasta(x->c, names, name_off, n_names, nullptr, 0, fd);
+  });
+}
+
+int pg_region_gfa_seq(pg_ctx* x, const char* names, const int64_t* name_off, uint64_t n_names, char* out,
+                      uint64_t cap, uint64_t* n_bytes) {
+  return guard([&] {
+    if (!x || !n_bytes) throw pg::Error(PG_EINVAL, "pg_region_gfa_seq: bad arguments");
+    PG_HIP(hipSetDevice(x->c.device));
+    *n_bytes = pg::format_region_gfa(x->c, names, name_off, n_names, out, cap, -1, true);
+  });
+}
+
+int pg_region_gfa_seq_fd(pg_ctx* x, const char* names, const int64_t* name_off, uint64_t n_names, int fd,
+                         uint64_t* n_bytes) {
+  return guard([&] {
+    if (!x || !n_bytes || fd < 0) throw pg::Error(PG_EINVAL, "pg_region_gfa_seq_fd: bad arguments");
+    PG_HIP(hipSetDevice(x->c.device));
+    *n_bytes = pg::format_region_gfa(x->c, names, name_off, n_names, nullptr, 0, fd, true);
   });
 }
 

@@ -317,6 +317,15 @@ struct Ctx {
   uint64_t rg_nn = 0, rg_nl = 0, rg_np = 0, rg_nu = 0, rg_total = 0;
   uint64_t rg_names = 0;          // record names a GFA text needs
   bool rg_ready = false;
+  // ---- region sequences (pg_regionseq.hip): the result of the last pg_region_seqs
+  DevBuf rs_tab;                  // [n + 1] label, row, record, start, end, strand, len, gc, amb, offset, padded offset
+  DevBuf rs_blob;                 // the sequences, every entry's start padded to 16 bytes
+  uint64_t rs_n = 0, rs_bases = 0, rs_pad = 0;   // entries, letters, bytes of the padded blob
+  uint64_t rs_names = 0;          // record names a FASTA text needs
+  bool rs_ready = false;
+  Timer t_rs;                     // the decoder kernel of the last pg_region_seqs (HIP events on `stream`)
+  double ms_rs_decode = 0;
+  uint64_t rs_chunks = 0;         // its 16-letter chunks
 
   // ---- npz persistence (pg_persist.hip)
   DevBuf preload;                 // staged PreEnt pairs, OR-merged by every build
@@ -476,7 +485,25 @@ void region_paths(Ctx& c, int64_t* record, int64_t* strand, int64_t* lo, int64_t
                   uint64_t cap);
 uint64_t format_region_links(Ctx& c, char* out, uint64_t cap, int fd = -1);
 uint64_t format_region_gfa(Ctx& c, const char* names, const int64_t* name_off, uint64_t n_names, char* out,
-                           uint64_t cap, int fd = -1);
+                           uint64_t cap, int fd = -1, bool seq = false);
+
+// pg_regionseq.hip
+// One representative sequence per label of rows (h_rows5 NULL: the last row
+// pass), decoded from the parse's packed class stream; replaces the context's
+// previous sequences only when it succeeds.
+void region_seqs(Ctx& c, const int64_t* h_rows5, uint64_t n_rows, const int32_t* rec_group, uint64_t n_records,
+                 uint32_t n_groups, uint64_t* n_regions, uint64_t* n_bases, uint64_t* n_skipped);
+void region_seqs_table(Ctx& c, int64_t* label, int64_t* row, int64_t* record, int64_t* start, int64_t* end,
+                       int64_t* strand, uint64_t* len, uint64_t* gc, uint64_t* amb, uint64_t* offset, uint64_t cap);
+uint64_t region_seqs_bases(Ctx& c, uint8_t* out, uint64_t cap);
+uint64_t format_region_fasta(Ctx& c, const char* names, const int64_t* name_off, uint64_t n_names, char* out,
+                             uint64_t cap, int fd = -1);
+// for format_region_gfa's S lines: -22 unless the sequences are those of the graph's nodes (same labels,
+// len == max_len; checked on the device); the device column of their lengths; every sequence copied to
+// d_dst + d_dst_off[entry] on c.stream
+void region_seqs_match(Ctx& c, const char* what);
+const unsigned long long* region_seqs_len(Ctx& c);
+void region_seqs_copy(Ctx& c, const unsigned long long* d_dst_off, char* d_dst);
 
 // helpers
 inline uint64_t next_pow2(uint64_t x) {

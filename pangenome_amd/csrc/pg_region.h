@@ -1,0 +1,133 @@
+// pg_region.h — what the passes over the region rows share (pg_region.hip, the
+// region graph; pg_regionseq.hip, the region sequences): a tile of rows
+// through LDS, the wave reductions, the lanes of a wave grouped by label, the
+// signed decimals and the node table of the graph.
+#pragma once
+#include "pg_internal.h"
+#include "pg_prim.h"
+
+namespace pg {
+
+typedef unsigned long long ull;
+
+#define RG_BLOCK 256
+#define RG_AGG_MIN 4               // lanes of a wave sharing a label before one lane issues for them
+
+#define RG_LOOP(i, n) \
+  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < (n); i += (uint64_t)gridDim.x * blockDim.x)
+
+#define RG_ADD(p, v) (void)__hip_atomic_fetch_add((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+#define RG_MAX(p, v) (void)__hip_atomic_fetch_max((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+#define RG_MIN(p, v) (void)__hip_atomic_fetch_min((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+
+#define RG_LAUNCH(kern, grid, ...)                                                       \
+  do {                                                                                   \
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(RG_BLOCK), 0, c.stream, __VA_ARGS__);      \
+    PG_HIP(hipGetLastError());                                                           \
+  } while (0)
+
+struct RgRow {
+  long long rec, start, end, strand, label;
+};
+// One tile of RG_BLOCK rows (40 bytes each) and the row before it (the halo:
+// row tile * RG_BLOCK - 1, none for tile 0) through LDS, read as contiguous
+// 8-byte loads.  Every thread then takes its own row r and the row before it
+// p (has_prev: there is one).  Called by every thread of the block (two
+// barriers); returns whether the thread has a row.  lds: 5 * (RG_BLOCK + 1) words.
+__device__ __forceinline__ bool rg_load_tile(const long long* __restrict__ rows, uint64_t n, uint64_t tile,
+                                             long long* lds, RgRow& r, RgRow& p, bool& has_prev) {
+  const uint64_t base = tile * RG_BLOCK;                   // first row of the tile
+  const uint32_t halo = base ? 1u : 0u;
+  const uint32_t cnt = (uint32_t)(n - base < RG_BLOCK ? n - base : (uint64_t)RG_BLOCK);
+  const uint32_t nw = 5 * (cnt + halo);
+  const long long* src = rows + 5 * (base - halo);
+  __syncthreads();                                         // (the previous tile's readers are done)
+  for (uint32_t w = threadIdx.x; w < nw; w += RG_BLOCK) lds[w] = src[w];
+  __syncthreads();
+  const bool have = threadIdx.x < cnt;
+  has_prev = have && (threadIdx.x + halo) > 0;
+  if (have) {
+    const long long* q = lds + 5 * (threadIdx.x + halo);
+    r.rec = q[0]; r.start = q[1]; r.end = q[2]; r.strand = q[3]; r.label = q[4];
+    if (has_prev) { p.rec = q[-5]; p.start = q[-4]; p.end = q[-3]; p.strand = q[-2]; p.label = q[-1]; }
+  }
+  return have;
+}
+__device__ __forceinline__ ull rg_len(const RgRow& r) {
+  return r.end >= r.start ? (ull)r.end - (ull)r.start : (ull)r.start - (ull)r.end;
+}
+__device__ __forceinline__ ull rg_readlane64(ull v, int lane) {
+  const uint32_t lo = __builtin_amdgcn_readlane((int)(uint32_t)v, lane);
+  const uint32_t hi = __builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), lane);
+  return ((ull)hi << 32) | lo;
+}
+__device__ __forceinline__ ull rg_wave_sum(ull v) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+__device__ __forceinline__ ull rg_wave_max(ull v) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) { const ull w = __shfl_xor(v, o); v = w > v ? w : v; }
+  return v;
+}
+__device__ __forceinline__ ull rg_wave_min(ull v) {
+#pragma unroll
+  for (int o = 32; o; o >>= 1) { const ull w = __shfl_xor(v, o); v = w < v ? w : v; }
+  return v;
+}
+// The lanes of a wave grouped by label (todo: the lane takes part).  A label
+// held by RG_AGG_MIN lanes or more: agg(label, mine, leader) is called by
+// every lane of the wave (it may reduce across the wave; `leader` is one of
+// the lanes that hold the label).  Returns whether the lane is left to issue
+// its own atomics.  Every lane of the wave must call it.
+template <class Agg>
+__device__ __forceinline__ bool rg_by_label(bool todo, ull lab, Agg&& agg) {
+  const int lane = threadIdx.x & 63;
+  bool own = false;
+  for (;;) {
+    const ull open = __ballot(todo);
+    if (!open) break;
+    const int lead = __ffsll(open) - 1;
+    const ull lab0 = rg_readlane64(lab, lead);
+    const bool mine = todo && lab == lab0;
+    const ull m = __ballot(mine);
+    todo = todo && !mine;
+    if (__popcll(m) < RG_AGG_MIN) {
+      own = own || mine;
+      continue;
+    }
+    agg(lab0, mine, (ull)__popcll(m), lane == lead);
+  }
+  return own;
+}
+
+// signed decimals (a host row's start and end may be negative)
+__device__ __forceinline__ uint32_t ndig_s(long long v) { return v < 0 ? 1 + ndig(0ull - (ull)v) : ndig((ull)v); }
+__device__ __forceinline__ char* put_sdec(char* o, long long v) {
+  if (v < 0) { *o++ = '-'; return put_dec(o, 0ull - (ull)v); }
+  return put_dec(o, (ull)v);
+}
+template <size_t N>
+__device__ __forceinline__ char* put_lit(char* o, const char (&s)[N]) {
+#pragma unroll
+  for (size_t i = 0; i + 1 < N; ++i) o[i] = s[i];
+  return o + (N - 1);
+}
+
+// the node table of the region graph (c.rg_nodes, nn entries)
+struct RgNodes {
+  long long* label;
+  ull *rows, *maxlen;
+  uint32_t *nout, *nin;
+  static size_t bytes(uint64_t nn) { return 32 * nn + 64; }
+  RgNodes(const DevBuf& b, uint64_t nn) {
+    label = b.as<long long>();
+    rows = reinterpret_cast<ull*>(label + nn);
+    maxlen = rows + nn;
+    nout = reinterpret_cast<uint32_t*>(maxlen + nn);
+    nin = nout + nn;
+  }
+};
+
+}  // namespace pg

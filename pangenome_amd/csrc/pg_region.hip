@@ -43,15 +43,9 @@
 // the input alone, whatever the schedule.
 #include <cstring>
 
-#include "pg_internal.h"
-#include "pg_prim.h"
+#include "pg_region.h"
 
 namespace pg {
-
-typedef unsigned long long ull;
-
-#define RG_BLOCK 256
-#define RG_AGG_MIN 4               // lanes of a wave sharing a label before one lane issues for them
 
 #define RG_USED 1u                 // flag byte of a row: it is used
 #define RG_HEAD 2u                 //                     it starts a run
@@ -59,96 +53,6 @@ typedef unsigned long long ull;
 #define RG_LAST 2u                 //                      last of its path
 #define RG_LINK 1u                 // flag byte of a sorted pair: its key differs from the pair before
 #define RG_GCHG 2u                 //                             its (key, genome) differs
-
-#define RG_LOOP(i, n) \
-  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < (n); i += (uint64_t)gridDim.x * blockDim.x)
-
-#define RG_ADD(p, v) (void)__hip_atomic_fetch_add((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#define RG_MAX(p, v) (void)__hip_atomic_fetch_max((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-
-struct RgRow {
-  long long rec, start, end, strand, label;
-};
-// One tile of RG_BLOCK rows (40 bytes each) and the row before it (the halo:
-// row tile * RG_BLOCK - 1, none for tile 0) through LDS, read as contiguous
-// 8-byte loads.  Every thread then takes its own row r and the row before it
-// p (has_prev: there is one).  Called by every thread of the block (two
-// barriers); returns whether the thread has a row.  lds: 5 * (RG_BLOCK + 1) words.
-__device__ __forceinline__ bool rg_load_tile(const long long* __restrict__ rows, uint64_t n, uint64_t tile,
-                                             long long* lds, RgRow& r, RgRow& p, bool& has_prev) {
-  const uint64_t base = tile * RG_BLOCK;                   // first row of the tile
-  const uint32_t halo = base ? 1u : 0u;
-  const uint32_t cnt = (uint32_t)(n - base < RG_BLOCK ? n - base : (uint64_t)RG_BLOCK);
-  const uint32_t nw = 5 * (cnt + halo);
-  const long long* src = rows + 5 * (base - halo);
-  __syncthreads();                                         // (the previous tile's readers are done)
-  for (uint32_t w = threadIdx.x; w < nw; w += RG_BLOCK) lds[w] = src[w];
-  __syncthreads();
-  const bool have = threadIdx.x < cnt;
-  has_prev = have && (threadIdx.x + halo) > 0;
-  if (have) {
-    const long long* q = lds + 5 * (threadIdx.x + halo);
-    r.rec = q[0]; r.start = q[1]; r.end = q[2]; r.strand = q[3]; r.label = q[4];
-    if (has_prev) { p.rec = q[-5]; p.start = q[-4]; p.end = q[-3]; p.strand = q[-2]; p.label = q[-1]; }
-  }
-  return have;
-}
-__device__ __forceinline__ ull rg_len(const RgRow& r) {
-  return r.end >= r.start ? (ull)r.end - (ull)r.start : (ull)r.start - (ull)r.end;
-}
-__device__ __forceinline__ ull rg_readlane64(ull v, int lane) {
-  const uint32_t lo = __builtin_amdgcn_readlane((int)(uint32_t)v, lane);
-  const uint32_t hi = __builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), lane);
-  return ((ull)hi << 32) | lo;
-}
-__device__ __forceinline__ ull rg_wave_sum(ull v) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ ull rg_wave_max(ull v) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) { const ull w = __shfl_xor(v, o); v = w > v ? w : v; }
-  return v;
-}
-// The lanes of a wave grouped by label (todo: the lane takes part).  A label
-// held by RG_AGG_MIN lanes or more: agg(label, mine, leader) is called by
-// every lane of the wave (it may reduce across the wave; `leader` is one of
-// the lanes that hold the label).  Returns whether the lane is left to issue
-// its own atomics.  Every lane of the wave must call it.
-template <class Agg>
-__device__ __forceinline__ bool rg_by_label(bool todo, ull lab, Agg&& agg) {
-  const int lane = threadIdx.x & 63;
-  bool own = false;
-  for (;;) {
-    const ull open = __ballot(todo);
-    if (!open) break;
-    const int lead = __ffsll(open) - 1;
-    const ull lab0 = rg_readlane64(lab, lead);
-    const bool mine = todo && lab == lab0;
-    const ull m = __ballot(mine);
-    todo = todo && !mine;
-    if (__popcll(m) < RG_AGG_MIN) {
-      own = own || mine;
-      continue;
-    }
-    agg(lab0, mine, (ull)__popcll(m), lane == lead);
-  }
-  return own;
-}
-
-// signed decimals (a host row's start and end may be negative)
-__device__ __forceinline__ uint32_t ndig_s(long long v) { return v < 0 ? 1 + ndig(0ull - (ull)v) : ndig((ull)v); }
-__device__ __forceinline__ char* put_sdec(char* o, long long v) {
-  if (v < 0) { *o++ = '-'; return put_dec(o, 0ull - (ull)v); }
-  return put_dec(o, (ull)v);
-}
-template <size_t N>
-__device__ __forceinline__ char* put_lit(char* o, const char (&s)[N]) {
-#pragma unroll
-  for (size_t i = 0; i + 1 < N; ++i) o[i] = s[i];
-  return o + (N - 1);
-}
 
 // ------------------------------------------------------------ a. scan
 // rf[i] = RG_USED | RG_HEAD of row i; out[0] = 1 + the largest used label (0: none), out[1] = used rows,
@@ -299,19 +203,6 @@ __global__ void k_rg_linkfin(RgLinks T, const ull* __restrict__ lpos, const ull*
 }
 
 // ------------------------------------------------------------ d. nodes
-struct RgNodes {
-  long long* label;
-  ull *rows, *maxlen;
-  uint32_t *nout, *nin;
-  static size_t bytes(uint64_t nn) { return 32 * nn + 64; }
-  RgNodes(const DevBuf& b, uint64_t nn) {
-    label = b.as<long long>();
-    rows = reinterpret_cast<ull*>(label + nn);
-    maxlen = rows + nn;
-    nout = reinterpret_cast<uint32_t*>(maxlen + nn);
-    nin = nout + nn;
-  }
-};
 __global__ void __launch_bounds__(RG_BLOCK) k_rg_accum(const long long* __restrict__ rows, uint64_t n,
                                                        const uint8_t* __restrict__ rf, ull* d_rows, ull* d_max) {
   __shared__ long long lds[5 * (RG_BLOCK + 1)];
@@ -372,7 +263,7 @@ __global__ void k_rg_gather(RgNodes T, uint64_t nn, const ull* __restrict__ d_ro
 #define RG_LINKS_HEADER "#from\tto\tcount\tgenomes\n"
 #define RG_GFA_HEADER "H\tVN:Z:1.0\n"
 #define RG_S1 "S\t"
-#define RG_S2 "\t*\tLN:i:"
+#define RG_S2 "\tLN:i:"                // (after the label: a tab, then `*` or the sequence)
 #define RG_L1 "L\t"
 #define RG_L2 "\t+\t"
 #define RG_L3 "\t+\t0M\tRC:i:"
@@ -402,14 +293,17 @@ __device__ __forceinline__ uint64_t rg_path_of(const ull* __restrict__ first, ui
   }
   return lo;
 }
-// items: nn S lines, nl L lines, nu path steps
+// items: nn S lines, nl L lines, nu path steps.  slen null: an S line carries `*`; otherwise node i's
+// sequence of slen[i] letters, which this pass leaves a gap for (sdst[i]: where it starts in `out`)
 __global__ void k_rg_glen(RgNodes N, uint64_t nn, RgLinks T, uint64_t nl, const long long* __restrict__ step_label,
                           const uint8_t* __restrict__ step_flag, uint64_t nu, RgPaths P, uint64_t np,
-                          const long long* __restrict__ name_off, ull* __restrict__ len) {
+                          const long long* __restrict__ name_off, const ull* __restrict__ slen,
+                          ull* __restrict__ len) {
   RG_LOOP(i, nn + nl + nu) {
     ull v;
     if (i < nn) {
-      v = RG_LIT(RG_S1) + ndig((ull)N.label[i]) + RG_LIT(RG_S2) + ndig(N.maxlen[i]) + 1;
+      v = RG_LIT(RG_S1) + ndig((ull)N.label[i]) + 1 + (slen ? slen[i] : 1ull) + RG_LIT(RG_S2) +
+          ndig(N.maxlen[i]) + 1;
     } else if (i < nn + nl) {
       const uint64_t l = i - nn;
       v = RG_LIT(RG_L1) + ndig((ull)T.from[l]) + RG_LIT(RG_L2) + ndig((ull)T.to[l]) + RG_LIT(RG_L3) +
@@ -430,12 +324,20 @@ __global__ void k_rg_glen(RgNodes N, uint64_t nn, RgLinks T, uint64_t nl, const 
 __global__ void k_rg_gwrite(RgNodes N, uint64_t nn, RgLinks T, uint64_t nl, const long long* __restrict__ step_label,
                             const uint8_t* __restrict__ step_flag, uint64_t nu, RgPaths P, uint64_t np,
                             const char* __restrict__ names, const long long* __restrict__ name_off,
-                            const ull* __restrict__ off, char* __restrict__ out) {
+                            const ull* __restrict__ off, const ull* __restrict__ slen, ull* __restrict__ sdst,
+                            char* __restrict__ out) {
   RG_LOOP(i, nn + nl + nu) {
     char* o = out + off[i];
     if (i < nn) {
       o = put_lit(o, RG_S1);
       o = put_dec(o, (ull)N.label[i]);
+      *o++ = '\t';
+      if (slen) {
+        sdst[i] = (ull)(o - out);
+        o += slen[i];
+      } else {
+        *o++ = '*';
+      }
       o = put_lit(o, RG_S2);
       o = put_dec(o, N.maxlen[i]);
       *o = '\n';
@@ -472,12 +374,6 @@ __global__ void k_rg_gwrite(RgNodes N, uint64_t nn, RgLinks T, uint64_t nl, cons
     }
   }
 }
-
-#define RG_LAUNCH(kern, grid, ...)                                                       \
-  do {                                                                                   \
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(RG_BLOCK), 0, c.stream, __VA_ARGS__);      \
-    PG_HIP(hipGetLastError());                                                           \
-  } while (0)
 
 // off[0 .. n]: the flag bytes with `bit` set before each position (f[n] must be 0); returns off[n]
 struct RgBit {
@@ -724,10 +620,13 @@ uint64_t format_region_links(Ctx& c, char* out, uint64_t cap, int fd) {
 
 // the GFA text of the last region_graph with this call's record names (names[name_off[r] ..
 // name_off[r+1]) is record r's): its size (out null, fd < 0), copied into out, or written to fd
+// (seq: every S line carries its region's sequence, from the last region_seqs - pg_region_gfa_seq)
 uint64_t format_region_gfa(Ctx& c, const char* names, const int64_t* name_off, uint64_t n_names, char* out,
-                           uint64_t cap, int fd) {
-  const char* what = fd >= 0 ? "pg_region_gfa_fd" : "pg_region_gfa";
+                           uint64_t cap, int fd, bool seq) {
+  const char* what = seq ? (fd >= 0 ? "pg_region_gfa_seq_fd" : "pg_region_gfa_seq")
+                         : (fd >= 0 ? "pg_region_gfa_fd" : "pg_region_gfa");
   rg_need(c, what);
+  if (seq) region_seqs_match(c, what);
   if (!name_off) throw Error(-22, std::string(what) + ": name_off is NULL");
   if (n_names < c.rg_names)
     throw Error(-22, std::string(what) + ": " + std::to_string(n_names) + " names, the paths need " +
@@ -739,8 +638,9 @@ uint64_t format_region_gfa(Ctx& c, const char* names, const int64_t* name_off, u
   if (nbytes && !names) throw Error(-22, std::string(what) + ": names is NULL");
   const uint64_t nn = c.rg_nn, nl = c.rg_nl, nu = c.rg_nu, np = c.rg_np, items = nn + nl + nu;
   const size_t hdr = RG_LIT(RG_GFA_HEADER);
-  DevBuf nm, tlen, toff, text;
+  DevBuf nm, tlen, toff, text, sdst;
   uint64_t body = 0;
+  const ull* slen = seq ? region_seqs_len(c) : nullptr;
   RgNodes N(c.rg_nodes, nn);
   RgLinks T(c.rg_links, nl);
   RgPaths P(c.rg_paths, np);
@@ -755,7 +655,7 @@ uint64_t format_region_gfa(Ctx& c, const char* names, const int64_t* name_off, u
     tlen.reserve(8 * (items + 1));
     toff.reserve(8 * (items + 1));
     RG_LAUNCH(k_rg_glen, grid_for(items, RG_BLOCK, 8192), N, nn, T, nl, step_label, step_flag, nu, P, np, d_off,
-              tlen.as<ull>());
+              slen, tlen.as<ull>());
     body = excl_scan_total(c, tlen.as<ull>(), toff.as<ull>(), items);
   }
   const uint64_t total = hdr + body;
@@ -763,9 +663,11 @@ uint64_t format_region_gfa(Ctx& c, const char* names, const int64_t* name_off, u
   if (out && cap < total) throw Error(-34, std::string(what) + ": buffer too small");
   text.reserve(total + 16);
   PG_HIP(hipMemcpyAsync(text.p, RG_GFA_HEADER, hdr, hipMemcpyHostToDevice, c.stream));
+  if (seq) sdst.reserve(8 * (nn + 1));
   if (items)
     RG_LAUNCH(k_rg_gwrite, grid_for(items, RG_BLOCK, 8192), N, nn, T, nl, step_label, step_flag, nu, P, np, d_names,
-              d_off, toff.as<ull>(), text.as<char>() + hdr);
+              d_off, toff.as<ull>(), slen, sdst.as<ull>(), text.as<char>() + hdr);
+  if (seq) region_seqs_copy(c, sdst.as<ull>(), text.as<char>() + hdr);
   if (out) PG_HIP(hipMemcpyAsync(out, text.p, total, hipMemcpyDeviceToHost, c.stream));
   c.sync();
   if (!out) text_to_fd(c, text.as<uint8_t>(), total, fd, what);

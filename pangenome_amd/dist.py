@@ -1477,8 +1477,9 @@ def entry_point(argv, out=None, shard_factory=None, device=None, dev_index: int 
     qry, kmer, Ns = args["-i"], int(args["-k"]), host.eval_number(args["-n"])
     bkt, dbs, rbk, rc, rdb = args["-r"], args["-d"], args["-R"], int(args["-c"]), args["-D"]
     n_orders = compare_orders_arg(args)
-    # -l (the region graph) is single process only: merging the ranks' link tables needs per-(link, genome) pairs
-    if not qry or args["-a"] not in ("mcl", "cc") or n_orders is None or args["-l"] != "0":
+    # -l (the region graph) is single process only: merging the ranks' link tables needs per-(link, genome) pairs;
+    # so is -s (the region sequences): a label's representative may lie in another rank's records
+    if not qry or args["-a"] not in ("mcl", "cc") or n_orders is None or args["-l"] != "0" or args["-s"] != "0":
         if dist.get_rank() == 0:
             manual_print(out)
         raise SystemExit()

@@ -854,6 +854,29 @@ def write_region_files(prefix: str, write_links, write_gfa, table: dict, genome_
     whole("_fr_graph.npz", lambda f: np.savez(f, **arrays))
 
 
+REGION_SEQ_COLS = ("label", "row", "record", "start", "end", "strand", "len", "gc", "amb")
+
+
+def write_region_seq_files(prefix: str, write_fasta, table: dict, ids, write_gfa=None) -> None:
+    """The `-s` files of `prefix` (the input's path): `_fr_regions.fa`
+    (write_fasta(file) writes the text), `_fr_regions.tsv` from the table's
+    columns (a record is printed by its seqid, ids[record]) and, with
+    write_gfa, `_fr_graph_seq.gfa`; each is written to `.tmp` and renamed
+    when whole."""
+    def whole(suffix, fill):
+        fn = prefix + suffix
+        with open(fn + ".tmp", "wb") as f:
+            fill(f)
+        os.replace(fn + ".tmp", fn)
+    whole("_fr_regions.fa", write_fasta)
+    cols = [np.asarray(table[k]).tolist() for k in REGION_SEQ_COLS]
+    whole("_fr_regions.tsv", lambda f: f.write(b"#label\trow\tseqid\tstart\tend\tstrand\tlen\tgc\tamb\n" + b"".join(
+        b"%d\t%d\t%s\t%d\t%d\t%d\t%d\t%d\t%d\n" % (l, r, bytes(ids[rec]), s, e, st, n, gc, amb)
+        for l, r, rec, s, e, st, n, gc, amb in zip(*cols))))
+    if write_gfa is not None:
+        whole("_fr_graph_seq.gfa", write_gfa)
+
+
 def seqid(name: bytes) -> bytes:
     """A record's id: its header without '>' up to the first whitespace."""
     p = bytes(name).split(None, 1)

@@ -9,7 +9,7 @@ runs in libpangenome_hip.so on an MI355X (pangenome_amd/csrc).  Mirrors:
   dbg2rdbg     :1313-1321                rdBG (K5 degree scan + compaction)
   seq2graph    :1853-1951                edges -> .xyz -> mcl -> labels -> rows
   dump / load_on_disk  :243-335         `<in>_db.npz` (oakht slot layout)
-  entry_point  :1971-2146                CLI (-i -k -n -c -r -d -R -D; ours: -a -w -g -p -l)
+  entry_point  :1971-2146                CLI (-i -k -n -c -r -d -R -D; ours: -a -w -g -p -l -s)
 
 Usage:  python -m pangenome_amd -i genomes.fa -k 27 > result.tab
 """
@@ -257,7 +257,7 @@ def rdbg_edges(g: DeviceGraph, Ns, chunk, rc, brkpt="", keep_on_device=False):
 
 def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_dict=None, saved=None,
               hashfunc=None, jit=True, chunk=2 ** 33, rc=False, cluster=True, out=None, min_weight=1, groups=None,
-              orders=0, links=False):
+              orders=0, links=False, seqs=False):
     """:1853-1951: edge weights -> `<qry>_rdbg_weight.xyz` -> mcl (or reuse)
     -> label dictionary -> print the region rows.  The edges, the label
     table, the rows and both texts are made on the device; the host writes
@@ -271,7 +271,10 @@ def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_
     compared on the device table (pg_freq_compare) over that many genome
     orders and four more `<qry>_fr_*` files written.  links (-l, with groups):
     the region graph of the device rows (pg_region_graph) is made with the
-    same genomes and its four `<qry>_fr_*` files written."""
+    same genomes and its four `<qry>_fr_*` files written.  seqs (-s, with
+    groups): one representative sequence per label is decoded on the device
+    (pg_region_seqs) and `<qry>_fr_regions.fa`, `_fr_regions.tsv` and, with
+    links, `_fr_graph_seq.gfa` written."""
     out = out or sys.stdout
     g = rdbg_dict
     res = rdbg_edges(g, Ns, chunk, rc, brkpt=brkpt, keep_on_device=True)
@@ -324,6 +327,8 @@ def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_
             write_compare(g, qry, gnames, int(orders))
         if links:
             write_region(g, qry, names, flags, groups)
+        if seqs:
+            write_region_seqs(g, qry, names, flags, groups, bool(links))
     gen = g.ctx.label_gen
     return LabelTable(loader=lambda: g.ctx.labels(gen))           # (raises once a later label pass replaced it)
 
@@ -390,6 +395,26 @@ def write_region(g, qry, names, flags, groups):
     host.write_region_files(qry, links, gfa, table, gnames)
 
 
+def write_region_seqs(g, qry, names, flags, groups, with_graph):
+    """-s: one representative sequence per label of the row pass just run
+    (pg_region_seqs on the device rows, write_freq's genomes) as
+    `<qry>_fr_regions.fa` (the device text; a record is named by its seqid),
+    `_fr_regions.tsv` and, after write_region (-l), `_fr_graph_seq.gfa`: the
+    graph with the sequences on its S lines."""
+    rec_group, gnames = host.assign_groups(names, flags, groups)
+    g.ctx.region_seqs(rec_group, len(gnames))
+    ids = [host.seqid(x) for x in names]
+
+    def fasta(f):
+        f.flush()
+        g.ctx.region_fasta_write(ids, f.fileno())
+
+    def gfa(f):
+        f.flush()
+        g.ctx.region_gfa_seq_write(ids, f.fileno())
+    host.write_region_seq_files(qry, fasta, g.ctx.region_seqs_table(), ids, gfa if with_graph else None)
+
+
 def _fileno(out):
     """The descriptor under a text stream's binary buffer (stdout, a file),
     or None (a stand-in with no descriptor)."""
@@ -407,6 +432,8 @@ def manual_print(out=None):
                  "  -d: the de bruijn graph", "  -r: break point of de bruijn graph",
                  "  -D: the reduced de bruijn graph", "  -R: break point of reduced de bruijn graph",
                  "  -n: length of query sequences for pan-genomic analysis",
+                 "  -s: with -g, one representative sequence per region. 0 (off) or 1; single process only. writes",
+                 "      <in>_fr_regions.fa, _fr_regions.tsv and, with -l 1, _fr_graph_seq.gfa (GFA 1 with sequences)",
                  "  -g: frequency table of the regions across genomes. record (each record a genome) or a file of",
                  "      seqid<TAB>genome lines; writes <in>_fr_freq.tsv, _fr_spectrum.tsv, _fr_genomes.tsv, _fr_presence.npz",
                  "  -p: with -g, compare the genomes over this many genome orders (0: off). writes <in>_fr_shared.tsv,",
@@ -422,7 +449,7 @@ def manual_print(out=None):
 def parse_args(argv):
     """:1983-1997 — same flag handling, including `-k27` and skipped unknowns."""
     args = {"-i": "", "-k": "50", "-n": "2**63", "-r": "", "-d": "", "-R": "", "-D": "", "-c": "2", "-a": "mcl",
-            "-w": "1", "-g": "", "-p": "0", "-l": "0"}
+            "-w": "1", "-g": "", "-p": "0", "-l": "0", "-s": "0"}
     N = len(argv)
     for i in range(1, N):
         k = argv[i]
@@ -451,13 +478,21 @@ def links_arg(args):
     return None if args["-l"] == "1" and not args["-g"] else args["-l"] == "1"
 
 
+def seqs_arg(args):
+    """-s's value: False (0) or True (1), or None for a value that is refused
+    - anything else, or 1 without -g."""
+    if args["-s"] not in ("0", "1"):
+        return None
+    return None if args["-s"] == "1" and not args["-g"] else args["-s"] == "1"
+
+
 def entry_point(argv, out=None, device=0):
     out = out or sys.stdout
     args = parse_args(argv)
     qry, kmer, Ns = args["-i"], int(args["-k"]), host.eval_number(args["-n"])
     bkt, dbs, rbk, rc, rdb = args["-r"], args["-d"], args["-R"], int(args["-c"]), args["-D"]
-    n_orders, links = compare_orders_arg(args), links_arg(args)
-    if not qry or args["-a"] not in ("mcl", "cc") or n_orders is None or links is None:
+    n_orders, links, seqs = compare_orders_arg(args), links_arg(args), seqs_arg(args)
+    if not qry or args["-a"] not in ("mcl", "cc") or n_orders is None or links is None or seqs is None:
         manual_print(out)
         raise SystemExit()
     clu = dict(cluster="cc", min_weight=int(args["-w"])) if args["-a"] == "cc" else {}
@@ -468,6 +503,8 @@ def entry_point(argv, out=None, device=0):
         clu["orders"] = n_orders
     if links:
         clu["links"] = True
+    if seqs:
+        clu["seqs"] = True
     # a group file is checked against the records before anything is built
     chk = (lambda g: check_groups(g, Ns, grp)) if grp and grp != "record" else None
     chunk = 2 ** 33
