@@ -190,6 +190,46 @@ def _names_blob(names: list):
     return (np.frombuffer(blob, np.uint8) if blob else np.zeros(1, np.uint8)), off
 
 
+def _names_args(names: list):
+    """The leading arguments of a text call that takes record names."""
+    return (*_names_blob(names), len(names))
+
+
+def _row_args(rec_group, rows):
+    """(rows5, n_rows, rec_group, n_records) as a row pass takes them
+    (pg_freq, pg_region_graph, pg_region_seqs); rows None: the device rows."""
+    grp = np.ascontiguousarray(rec_group, dtype=np.int32).reshape(-1)
+    n_records = grp.shape[0]
+    if not n_records:
+        grp = np.full(1, -1, np.int32)               # (never NULL: an empty array's pointer may be)
+    r5, n_rows = None, 0
+    if rows is not None:
+        r5 = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1, 5)
+        n_rows = r5.shape[0]
+        if not n_rows:
+            r5 = np.zeros((1, 5), np.int64)          # (NULL would mean the device rows)
+    return r5, n_rows, grp, n_records
+
+
+def _text(h, fn, what, *lead) -> bytes:
+    """The bytes of a size-then-fill call fn(h, *lead, out, cap, &n); an
+    array in lead goes as its pointer."""
+    lead = [ptr(a) if isinstance(a, np.ndarray) else a for a in lead]
+    n = C.c_uint64()
+    check(fn(h, *lead, None, 0, C.byref(n)), what)
+    buf = np.empty(max(n.value, 1), np.uint8)
+    check(fn(h, *lead, ptr(buf), buf.shape[0], C.byref(n)), what)
+    return buf[:n.value].tobytes()
+
+
+def _write(h, fn, what, fd, *lead) -> int:
+    """fn(h, *lead, fd, &n): the text written to descriptor fd; its bytes."""
+    lead = [ptr(a) if isinstance(a, np.ndarray) else a for a in lead]
+    n = C.c_uint64()
+    check(fn(h, *lead, int(fd), C.byref(n)), what)
+    return n.value
+
+
 class Context:
     """One pg_ctx: one HIP device, one stream, all device buffers."""
 
@@ -488,19 +528,13 @@ class Context:
     def edges_text(self) -> bytes:
         """The `.xyz` text of the last edges() pass (first-occurrence order),
         formatted on the device (pg_edges_format)."""
-        n = C.c_uint64()
-        check(self.lib.pg_edges_format(self.h, None, 0, C.byref(n)), "pg_edges_format")
-        buf = np.empty(max(n.value, 1), np.uint8)
-        check(self.lib.pg_edges_format(self.h, ptr(buf), buf.shape[0], C.byref(n)), "pg_edges_format")
-        return buf[:n.value].tobytes()
+        return _text(self.h, self.lib.pg_edges_format, "pg_edges_format")
 
     def edges_write(self, fd: int) -> int:
         """edges_text() written straight to descriptor fd at its position
         (pg_edges_format_fd: pinned pieces, parallel pwrite into a regular
         file); flush any buffered writer on fd first.  Returns the bytes."""
-        n = C.c_uint64()
-        check(self.lib.pg_edges_format_fd(self.h, int(fd), C.byref(n)), "pg_edges_format_fd")
-        return n.value
+        return _write(self.h, self.lib.pg_edges_format_fd, "pg_edges_format_fd", fd)
 
     def labels_from_edges(self, tuples=None, mcl_keys=None, mcl_vals=None, mcl_ids=None, next_label: int = 0):
         """seq2graph's label table on the device (pg_labels_from_edges): the
@@ -537,18 +571,12 @@ class Context:
 
     def clusters_text(self) -> bytes:
         """The `.mcl` text of the last cluster_cc (pg_clusters_format)."""
-        n = C.c_uint64()
-        check(self.lib.pg_clusters_format(self.h, None, 0, C.byref(n)), "pg_clusters_format")
-        buf = np.empty(max(n.value, 1), np.uint8)
-        check(self.lib.pg_clusters_format(self.h, ptr(buf), buf.shape[0], C.byref(n)), "pg_clusters_format")
-        return buf[:n.value].tobytes()
+        return _text(self.h, self.lib.pg_clusters_format, "pg_clusters_format")
 
     def clusters_write(self, fd: int) -> int:
         """clusters_text() written straight to descriptor fd at its position
         (pg_clusters_format_fd); flush any buffered writer on fd first."""
-        n = C.c_uint64()
-        check(self.lib.pg_clusters_format_fd(self.h, int(fd), C.byref(n)), "pg_clusters_format_fd")
-        return n.value
+        return _write(self.h, self.lib.pg_clusters_format_fd, "pg_clusters_format_fd", fd)
 
     def labels(self, gen=None):
         """(keys, vals, ids) of the device label table, in insertion order.
@@ -582,22 +610,12 @@ class Context:
     def rows_text(self, names: list) -> bytes:
         """The region rows' text of the last pg_rows, formatted on the device
         (pg_rows_format); names[r] = record r's qid."""
-        nb, off = _names_blob(names)
-        n = C.c_uint64()
-        check(self.lib.pg_rows_format(self.h, ptr(nb), ptr(off), len(names), None, 0, C.byref(n)), "pg_rows_format")
-        buf = np.empty(max(n.value, 1), np.uint8)
-        check(self.lib.pg_rows_format(self.h, ptr(nb), ptr(off), len(names), ptr(buf), buf.shape[0], C.byref(n)),
-              "pg_rows_format")
-        return buf[:n.value].tobytes()
+        return _text(self.h, self.lib.pg_rows_format, "pg_rows_format", *_names_args(names))
 
     def rows_write(self, names: list, fd: int) -> int:
         """rows_text(names) written straight to descriptor fd at its position
         (pg_rows_format_fd); flush any buffered writer on fd first."""
-        nb, off = _names_blob(names)
-        n = C.c_uint64()
-        check(self.lib.pg_rows_format_fd(self.h, ptr(nb), ptr(off), len(names), int(fd), C.byref(n)),
-              "pg_rows_format_fd")
-        return n.value
+        return _write(self.h, self.lib.pg_rows_format_fd, "pg_rows_format_fd", fd, *_names_args(names))
 
     def rows(self, rec_flags=None, rc1: bool = False):
         n = C.c_uint64()
@@ -615,16 +633,7 @@ class Context:
         r's genome in [0, n_groups) or -1.  Returns (n_labels, n_used,
         n_skipped); the table stays on the device (freq_table /
         freq_spectrum / freq_groups / freq_text / freq_write)."""
-        grp = np.ascontiguousarray(rec_group, dtype=np.int32).reshape(-1)
-        n_records = grp.shape[0]
-        if not n_records:
-            grp = np.full(1, -1, np.int32)           # (never NULL: an empty array's pointer may be)
-        r5, n_rows = None, 0
-        if rows is not None:
-            r5 = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1, 5)
-            n_rows = r5.shape[0]
-            if not n_rows:
-                r5 = np.zeros((1, 5), np.int64)      # (NULL would mean the device rows)
+        r5, n_rows, grp, n_records = _row_args(rec_group, rows)
         nl, nu, ns = C.c_uint64(), C.c_uint64(), C.c_uint64()
         check(self.lib.pg_freq(self.h, ptr(r5), n_rows, ptr(grp), n_records, int(n_groups),
                                C.byref(nl), C.byref(nu), C.byref(ns)), "pg_freq")
@@ -662,18 +671,12 @@ class Context:
 
     def freq_text(self) -> bytes:
         """The table's text, formatted on the device (pg_freq_format)."""
-        n = C.c_uint64()
-        check(self.lib.pg_freq_format(self.h, None, 0, C.byref(n)), "pg_freq_format")
-        buf = np.empty(max(n.value, 1), np.uint8)
-        check(self.lib.pg_freq_format(self.h, ptr(buf), buf.shape[0], C.byref(n)), "pg_freq_format")
-        return buf[:n.value].tobytes()
+        return _text(self.h, self.lib.pg_freq_format, "pg_freq_format")
 
     def freq_write(self, fd: int) -> int:
         """freq_text() written straight to descriptor fd at its position
         (pg_freq_format_fd); flush any buffered writer on fd first."""
-        n = C.c_uint64()
-        check(self.lib.pg_freq_format_fd(self.h, int(fd), C.byref(n)), "pg_freq_format_fd")
-        return n.value
+        return _write(self.h, self.lib.pg_freq_format_fd, "pg_freq_format_fd", fd)
 
     # ---------------------------------------------------- genome comparison
     def freq_compare(self, orders, bits=None, n_groups=None):
@@ -721,16 +724,7 @@ class Context:
         freq() takes it.  Returns (n_nodes, n_links, n_paths, n_skipped); the
         graph stays on the device (region_nodes / region_links / region_paths
         / region_links_text / region_gfa_text and their _write forms)."""
-        grp = np.ascontiguousarray(rec_group, dtype=np.int32).reshape(-1)
-        n_records = grp.shape[0]
-        if not n_records:
-            grp = np.full(1, -1, np.int32)           # (never NULL: an empty array's pointer may be)
-        r5, n_rows = None, 0
-        if rows is not None:
-            r5 = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1, 5)
-            n_rows = r5.shape[0]
-            if not n_rows:
-                r5 = np.zeros((1, 5), np.int64)      # (NULL would mean the device rows)
+        r5, n_rows, grp, n_records = _row_args(rec_group, rows)
         nn, nl, npth, ns = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
         check(self.lib.pg_region_graph(self.h, ptr(r5), n_rows, ptr(grp), n_records, int(n_groups),
                                        C.byref(nn), C.byref(nl), C.byref(npth), C.byref(ns)), "pg_region_graph")
@@ -769,38 +763,22 @@ class Context:
 
     def region_links_text(self) -> bytes:
         """The links table's text, formatted on the device (pg_region_links_format)."""
-        n = C.c_uint64()
-        check(self.lib.pg_region_links_format(self.h, None, 0, C.byref(n)), "pg_region_links_format")
-        buf = np.empty(max(n.value, 1), np.uint8)
-        check(self.lib.pg_region_links_format(self.h, ptr(buf), buf.shape[0], C.byref(n)), "pg_region_links_format")
-        return buf[:n.value].tobytes()
+        return _text(self.h, self.lib.pg_region_links_format, "pg_region_links_format")
 
     def region_links_write(self, fd: int) -> int:
         """region_links_text() written straight to descriptor fd at its
         position (pg_region_links_format_fd); flush any buffered writer on fd first."""
-        n = C.c_uint64()
-        check(self.lib.pg_region_links_format_fd(self.h, int(fd), C.byref(n)), "pg_region_links_format_fd")
-        return n.value
+        return _write(self.h, self.lib.pg_region_links_format_fd, "pg_region_links_format_fd", fd)
 
     def region_gfa_text(self, names: list) -> bytes:
         """The graph as GFA 1, formatted on the device (pg_region_gfa);
         names[r] = record r's name in the path lines."""
-        nb, off = _names_blob(names)
-        n = C.c_uint64()
-        check(self.lib.pg_region_gfa(self.h, ptr(nb), ptr(off), len(names), None, 0, C.byref(n)), "pg_region_gfa")
-        buf = np.empty(max(n.value, 1), np.uint8)
-        check(self.lib.pg_region_gfa(self.h, ptr(nb), ptr(off), len(names), ptr(buf), buf.shape[0], C.byref(n)),
-              "pg_region_gfa")
-        return buf[:n.value].tobytes()
+        return _text(self.h, self.lib.pg_region_gfa, "pg_region_gfa", *_names_args(names))
 
     def region_gfa_write(self, names: list, fd: int) -> int:
         """region_gfa_text(names) written straight to descriptor fd at its
         position (pg_region_gfa_fd); flush any buffered writer on fd first."""
-        nb, off = _names_blob(names)
-        n = C.c_uint64()
-        check(self.lib.pg_region_gfa_fd(self.h, ptr(nb), ptr(off), len(names), int(fd), C.byref(n)),
-              "pg_region_gfa_fd")
-        return n.value
+        return _write(self.h, self.lib.pg_region_gfa_fd, "pg_region_gfa_fd", fd, *_names_args(names))
 
     # ---------------------------------------------------- region sequences
     def region_seqs(self, rec_group, n_groups: int, rows=None):
@@ -810,16 +788,7 @@ class Context:
         takes it.  Returns (n_regions, n_bases, n_skipped); the result stays
         on the device (region_seqs_table / region_seqs_bases /
         region_fasta_text / region_gfa_seq_text and their _write forms)."""
-        grp = np.ascontiguousarray(rec_group, dtype=np.int32).reshape(-1)
-        n_records = grp.shape[0]
-        if not n_records:
-            grp = np.full(1, -1, np.int32)           # (never NULL: an empty array's pointer may be)
-        r5, n_rows = None, 0
-        if rows is not None:
-            r5 = np.ascontiguousarray(rows, dtype=np.int64).reshape(-1, 5)
-            n_rows = r5.shape[0]
-            if not n_rows:
-                r5 = np.zeros((1, 5), np.int64)      # (NULL would mean the device rows)
+        r5, n_rows, grp, n_records = _row_args(rec_group, rows)
         nr, nb, ns = C.c_uint64(), C.c_uint64(), C.c_uint64()
         check(self.lib.pg_region_seqs(self.h, ptr(r5), n_rows, ptr(grp), n_records, int(n_groups),
                                       C.byref(nr), C.byref(nb), C.byref(ns)), "pg_region_seqs")
@@ -839,11 +808,7 @@ class Context:
     def region_seqs_bases(self) -> bytes:
         """The sequences one after another in table order, no separators
         (pg_region_seqs_bases)."""
-        n = C.c_uint64()
-        check(self.lib.pg_region_seqs_bases(self.h, None, 0, C.byref(n)), "pg_region_seqs_bases")
-        buf = np.empty(max(n.value, 1), np.uint8)
-        check(self.lib.pg_region_seqs_bases(self.h, ptr(buf), buf.shape[0], C.byref(n)), "pg_region_seqs_bases")
-        return buf[:n.value].tobytes()
+        return _text(self.h, self.lib.pg_region_seqs_bases, "pg_region_seqs_bases")
 
     def region_seqs_time(self):
         """(ms, chunks): the decoder kernel's time in the last region_seqs()
@@ -852,40 +817,26 @@ class Context:
         check(self.lib.pg_region_seqs_time(self.h, C.byref(ms), C.byref(n)), "pg_region_seqs_time")
         return ms.value, n.value
 
-    def _names_text(self, fn, what, names) -> bytes:
-        nb, off = _names_blob(names)
-        n = C.c_uint64()
-        check(fn(self.h, ptr(nb), ptr(off), len(names), None, 0, C.byref(n)), what)
-        buf = np.empty(max(n.value, 1), np.uint8)
-        check(fn(self.h, ptr(nb), ptr(off), len(names), ptr(buf), buf.shape[0], C.byref(n)), what)
-        return buf[:n.value].tobytes()
-
-    def _names_write(self, fn, what, names, fd) -> int:
-        nb, off = _names_blob(names)
-        n = C.c_uint64()
-        check(fn(self.h, ptr(nb), ptr(off), len(names), int(fd), C.byref(n)), what)
-        return n.value
-
     def region_fasta_text(self, names: list) -> bytes:
         """The sequences as FASTA, formatted on the device (pg_region_fasta);
         names[r] = record r's name in the header lines."""
-        return self._names_text(self.lib.pg_region_fasta, "pg_region_fasta", names)
+        return _text(self.h, self.lib.pg_region_fasta, "pg_region_fasta", *_names_args(names))
 
     def region_fasta_write(self, names: list, fd: int) -> int:
         """region_fasta_text(names) written straight to descriptor fd at its
         position (pg_region_fasta_fd); flush any buffered writer on fd first."""
-        return self._names_write(self.lib.pg_region_fasta_fd, "pg_region_fasta_fd", names, fd)
+        return _write(self.h, self.lib.pg_region_fasta_fd, "pg_region_fasta_fd", fd, *_names_args(names))
 
     def region_gfa_seq_text(self, names: list) -> bytes:
         """region_gfa_text(names) with every S line carrying its sequence
         (pg_region_gfa_seq): needs region_graph() and region_seqs() of the
         same rows and groups."""
-        return self._names_text(self.lib.pg_region_gfa_seq, "pg_region_gfa_seq", names)
+        return _text(self.h, self.lib.pg_region_gfa_seq, "pg_region_gfa_seq", *_names_args(names))
 
     def region_gfa_seq_write(self, names: list, fd: int) -> int:
         """region_gfa_seq_text(names) written straight to descriptor fd at its
         position (pg_region_gfa_seq_fd); flush any buffered writer on fd first."""
-        return self._names_write(self.lib.pg_region_gfa_seq_fd, "pg_region_gfa_seq_fd", names, fd)
+        return _write(self.h, self.lib.pg_region_gfa_seq_fd, "pg_region_gfa_seq_fd", fd, *_names_args(names))
 
     def rows_export(self, n: int):
         """The [n, 5] rows of the last rows_count() (pg_rows_export)."""

@@ -27,28 +27,25 @@
 
 namespace pg {
 
-#define CC_LOOP(i, n) \
-  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < (n); i += (uint64_t)gridDim.x * blockDim.x)
-
 // ------------------------------------------------------------ node ids
 // slots sorted by (key, value), stably: a group's first slot is the node's first appearance
 __global__ void k_cc_heads(const unsigned long long* __restrict__ skey, const unsigned long long* __restrict__ pos,
                            const unsigned* __restrict__ val0, uint64_t n, uint8_t* __restrict__ head,
                            unsigned* __restrict__ head32) {
-  CC_LOOP(t, n) {
+  RG_LOOP(t, n) {
     const bool h = t == 0 || skey[t - 1] != skey[t] || val0[pos[t - 1]] != val0[pos[t]];
     head[t] = h;
     head32[t] = h;
   }
 }
 __global__ void k_cc_iota32(unsigned* __restrict__ out, uint64_t n) {
-  CC_LOOP(i, n) out[i] = (unsigned)i;
+  RG_LOOP(i, n) out[i] = (unsigned)i;
 }
 // groups ordered by first appearance: group gsorted[r] is node r
 __global__ void k_cc_rank(const unsigned long long* __restrict__ fsorted, const unsigned* __restrict__ gsorted,
                           uint64_t nu, const unsigned long long* __restrict__ tup, unsigned* __restrict__ rank_of_group,
                           unsigned long long* __restrict__ nkey, unsigned long long* __restrict__ nval) {
-  CC_LOOP(r, nu) {
+  RG_LOOP(r, nu) {
     rank_of_group[gsorted[r]] = (unsigned)r;
     const unsigned long long t = fsorted[r];
     nkey[r] = tup[2 * t];
@@ -58,12 +55,12 @@ __global__ void k_cc_rank(const unsigned long long* __restrict__ fsorted, const 
 __global__ void k_cc_ids(const unsigned long long* __restrict__ pos, const unsigned* __restrict__ gx,
                          const unsigned* __restrict__ head32, uint64_t nn, const unsigned* __restrict__ rank_of_group,
                          unsigned* __restrict__ id) {
-  CC_LOOP(t, nn) id[pos[t]] = rank_of_group[gx[t] + head32[t] - 1u];
+  RG_LOOP(t, nn) id[pos[t]] = rank_of_group[gx[t] + head32[t] - 1u];
 }
 
 // ------------------------------------------------------------ union-find
 __global__ void k_cc_init(unsigned* __restrict__ parent, uint64_t nu) {
-  CC_LOOP(i, nu) parent[i] = (unsigned)i;
+  RG_LOOP(i, nu) parent[i] = (unsigned)i;
 }
 
 __device__ __forceinline__ unsigned cc_load(const unsigned* p) {
@@ -82,7 +79,7 @@ __device__ __forceinline__ unsigned cc_find(unsigned* parent, unsigned x) {
 
 __global__ void k_cc_hook(const unsigned* __restrict__ id, const long long* __restrict__ cnt, uint64_t ne,
                           long long min_weight, unsigned* parent) {
-  CC_LOOP(e, ne) {
+  RG_LOOP(e, ne) {
     if (cnt[e] < min_weight) continue;
     unsigned a = id[2 * e], b = id[2 * e + 1];
     if (a == b) continue;
@@ -108,22 +105,22 @@ __global__ void k_cc_hook(const unsigned* __restrict__ id, const long long* __re
 // numbered in walk order, so the hooked trees are deep: one thread walking
 // to its root took 10.9 ms of dependent loads on C3's table.)
 __global__ void k_cc_jump(const unsigned* __restrict__ in, uint64_t nu, unsigned* __restrict__ out) {
-  CC_LOOP(i, nu) out[i] = in[in[i]];
+  RG_LOOP(i, nu) out[i] = in[in[i]];
 }
 
 // ------------------------------------------------------------ order
 // roots and sizes (the run lengths of the sorted comp[]) -> sort keys: size descending, root ascending
 __global__ void k_cc_rootkeys(const unsigned* __restrict__ root, const unsigned* __restrict__ size, uint64_t nc,
                               unsigned long long* __restrict__ rkey) {
-  CC_LOOP(r, nc) rkey[r] = ((unsigned long long)(0xFFFFFFFFu - size[r]) << 32) | (unsigned long long)root[r];
+  RG_LOOP(r, nc) rkey[r] = ((unsigned long long)(0xFFFFFFFFu - size[r]) << 32) | (unsigned long long)root[r];
 }
 __global__ void k_cc_lines(const unsigned long long* __restrict__ rsorted, uint64_t nc,
                            unsigned* __restrict__ line_of_root) {
-  CC_LOOP(r, nc) line_of_root[(unsigned)rsorted[r]] = (unsigned)r;
+  RG_LOOP(r, nc) line_of_root[(unsigned)rsorted[r]] = (unsigned)r;
 }
 __global__ void k_cc_nodeline(const unsigned* __restrict__ comp, const unsigned* __restrict__ line_of_root, uint64_t nu,
                               unsigned* __restrict__ nl, unsigned* __restrict__ ni) {
-  CC_LOOP(i, nu) {
+  RG_LOOP(i, nu) {
     nl[i] = line_of_root[comp[i]];
     ni[i] = (unsigned)i;
   }
@@ -133,13 +130,13 @@ __global__ void k_cc_nodeline(const unsigned* __restrict__ comp, const unsigned*
 // token j of the file: node sm[j] as "<key>_<value>" and one separator
 __global__ void k_mcl_len(const unsigned long long* __restrict__ nkey, const unsigned long long* __restrict__ nval,
                           const unsigned* __restrict__ sm, uint64_t nu, unsigned long long* __restrict__ len) {
-  CC_LOOP(j, nu) len[j] = ndig(nkey[sm[j]]) + ndig(nval[sm[j]]) + 2;
+  RG_LOOP(j, nu) len[j] = ndig(nkey[sm[j]]) + ndig(nval[sm[j]]) + 2;
 }
 __global__ void k_mcl_write(const unsigned long long* __restrict__ nkey, const unsigned long long* __restrict__ nval,
                             const unsigned* __restrict__ sm, const unsigned* __restrict__ sl, uint64_t nu,
                             const unsigned long long* __restrict__ off, char* __restrict__ out,
                             long long* __restrict__ lkey, long long* __restrict__ lval, long long* __restrict__ lid) {
-  CC_LOOP(j, nu) {
+  RG_LOOP(j, nu) {
     const unsigned m = sm[j];
     char* o = out + off[j];
     o = put_dec(o, nkey[m]); *o++ = '_'; o = put_dec(o, nval[m]);
@@ -150,11 +147,8 @@ __global__ void k_mcl_write(const unsigned long long* __restrict__ nkey, const u
   }
 }
 
-#define CC_LAUNCH(kern, n, ...)                                                                       \
-  do {                                                                                                \
-    hipLaunchKernelGGL(kern, dim3(grid_for((n), 256, 8192)), dim3(256), 0, c.stream, __VA_ARGS__);    \
-    PG_HIP(hipGetLastError());                                                                        \
-  } while (0)
+// one thread per item of n, up to 8192 blocks
+#define CC_LAUNCH(kern, n, ...) RG_LAUNCH(kern, grid_for((n), RG_BLOCK, 8192), __VA_ARGS__)
 
 void cluster_cc(Ctx& c, const uint64_t* h_tuples, const int64_t* h_counts, uint64_t n_edges, int64_t min_weight) {
   DevBuf up;
@@ -305,17 +299,7 @@ void cluster_cc(Ctx& c, const uint64_t* h_tuples, const int64_t* h_counts, uint6
 // into out, or written to descriptor fd
 uint64_t format_clusters(Ctx& c, char* out, uint64_t cap, int fd) {
   if (!c.clu_ready) throw Error(-22, "pg_clusters_format: no clustering (call pg_cluster_cc first)");
-  if (!out && fd < 0) return c.clu_total;
-  if (out && cap < c.clu_total) throw Error(-34, "pg_clusters_format: buffer too small");
-  if (c.clu_total) {
-    if (out) {
-      PG_HIP(hipMemcpyAsync(out, c.clu_text.p, c.clu_total, hipMemcpyDeviceToHost, c.stream));
-      c.sync();
-    } else {
-      text_to_fd(c, c.clu_text.as<uint8_t>(), c.clu_total, fd, "pg_clusters_format_fd");
-    }
-  }
-  return c.clu_total;
+  return text_out(c, c.clu_text.p, c.clu_total, out, cap, fd, "pg_clusters_format", "pg_clusters_format_fd");
 }
 
 }  // namespace pg

@@ -23,14 +23,9 @@
 #include <cstring>
 #include <vector>
 
-#include "pg_internal.h"
+#include "pg_prim.h"
 
 namespace pg {
-
-typedef unsigned long long ull;
-
-#define CMP_BLOCK 256
-#define CMP_ADD(p, v) (void)__hip_atomic_fetch_add((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
 
 #define CMP_MAX_GROUPS 32768u      // the matrix is dense: 8 GiB at this size
 #define CMP_MAX_CHUNK (1u << 25)   // words per k_cmp_shared block: 64 x 2^25 = 2^31 bits, a 32-bit sum cannot wrap
@@ -45,7 +40,7 @@ typedef unsigned long long ull;
 // of a store group then fall on 16 different bank pairs.)
 #define TR_WORDS 16
 #define TR_STRIDE (TR_WORDS + 1)
-__global__ void __launch_bounds__(CMP_BLOCK) k_cmp_transpose(const ull* __restrict__ bits, uint64_t n, uint32_t W,
+__global__ void __launch_bounds__(RG_BLOCK) k_cmp_transpose(const ull* __restrict__ bits, uint64_t n, uint32_t W,
                                                              uint32_t G, uint64_t NW, ull* __restrict__ T) {
   __shared__ ull lds[64 * TR_STRIDE];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -54,7 +49,7 @@ __global__ void __launch_bounds__(CMP_BLOCK) k_cmp_transpose(const ull* __restri
     const uint64_t tile = item / W;
     const uint32_t w = (uint32_t)(item - tile * W);
     __syncthreads();                                       // (the previous item's readers are done)
-    for (int k = wave; k < TR_WORDS; k += CMP_BLOCK / 64) {
+    for (int k = wave; k < TR_WORDS; k += RG_BLOCK / 64) {
       const uint64_t l = (tile * TR_WORDS + k) * 64 + lane;
       const ull v = l < n ? bits[l * W + w] : 0ull;        // labels >= n: 0
       ull mine = 0;
@@ -66,7 +61,7 @@ __global__ void __launch_bounds__(CMP_BLOCK) k_cmp_transpose(const ull* __restri
       lds[lane * TR_STRIDE + k] = mine;
     }
     __syncthreads();
-    for (int i = threadIdx.x; i < 64 * TR_WORDS; i += CMP_BLOCK) {
+    for (int i = threadIdx.x; i < 64 * TR_WORDS; i += RG_BLOCK) {
       const int r = i / TR_WORDS, k = i % TR_WORDS;
       const uint32_t g = w * 64 + (uint32_t)r;
       const uint64_t col = tile * TR_WORDS + (uint64_t)k;
@@ -87,13 +82,13 @@ __global__ void __launch_bounds__(CMP_BLOCK) k_cmp_transpose(const ull* __restri
 #define SH_STRIDE (SH_KT + 1)
 __device__ __forceinline__ void cmp_load_panel(const ull* __restrict__ T, uint64_t NW, uint32_t G, uint32_t row0,
                                                uint64_t w0, uint64_t w1, ull* lds) {
-  for (int i = threadIdx.x; i < 64 * SH_KT; i += CMP_BLOCK) {
+  for (int i = threadIdx.x; i < 64 * SH_KT; i += RG_BLOCK) {
     const uint32_t r = i / SH_KT, k = i % SH_KT;
     const uint32_t g = row0 + r;
     lds[r * SH_STRIDE + k] = (g < G && w0 + k < w1) ? T[(uint64_t)g * NW + w0 + k] : 0ull;
   }
 }
-__global__ void __launch_bounds__(CMP_BLOCK) k_cmp_shared(const ull* __restrict__ T, uint64_t NW, uint32_t G,
+__global__ void __launch_bounds__(RG_BLOCK) k_cmp_shared(const ull* __restrict__ T, uint64_t NW, uint32_t G,
                                                           uint32_t nT, uint32_t nU, uint64_t cw,
                                                           ull* __restrict__ shared) {
   __shared__ ull As[64 * SH_STRIDE];
@@ -129,7 +124,7 @@ __global__ void __launch_bounds__(CMP_BLOCK) k_cmp_shared(const ull* __restrict_
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const uint32_t g = tr * 64 + ty + 16 * i, h = tc * 64 + tx + 16 * j;
-      if (g < G && h < G && acc[i][j]) CMP_ADD(shared + (uint64_t)g * G + h, (ull)acc[i][j]);
+      if (g < G && h < G && acc[i][j]) RG_ADD(shared + (uint64_t)g * G + h, (ull)acc[i][j]);
     }
 }
 // the tiles below the diagonal from their mirror images
@@ -143,43 +138,43 @@ __global__ void k_cmp_mirror(ull* __restrict__ shared, uint32_t G) {
 
 // ------------------------------------------------------------ c. curves
 // Grid: column chunks x orders.  A lane owns CV_COLS word columns (w = base +
-// c * CMP_BLOCK + thread: a wave's loads of one row are contiguous) and walks
+// c * RG_BLOCK + thread: a wave's loads of one row are contiguous) and walks
 // the order: x = T[order[n]][w], or |= x, and &= x.  `and` starts as the
 // column's valid-label mask (all ones; the low n % 64 bits in the last word;
 // 0 in the padding), so labels that do not exist are never in the core.  The
 // two popcounts of a step are summed over the lane's columns and then over
 // the wave in one 32-bit word, 16 bits each: 64 lanes x CV_COLS x 64 bits =
 // 2^14 <= 2^15 while CV_COLS <= 8.  LDS form: the wave's sums go to per-block
-// 32-bit LDS counters [G][2] (a block covers CMP_BLOCK x CV_COLS x 64 = 2^16
+// 32-bit LDS counters [G][2] (a block covers RG_BLOCK x CV_COLS x 64 = 2^16
 // labels), flushed once with global 64-bit adds.  Above CMP_LDS_GROUPS genomes
 // (16 KiB of counters) the wave's sums go straight to global atomics.
 #define CV_COLS 4
 #define CMP_LDS_GROUPS 2048u
 template <bool LDS>
-__global__ void __launch_bounds__(CMP_BLOCK) k_cmp_curves(const ull* __restrict__ T, uint64_t NW, uint64_t n,
+__global__ void __launch_bounds__(RG_BLOCK) k_cmp_curves(const ull* __restrict__ T, uint64_t NW, uint64_t n,
                                                           uint32_t G, const int* __restrict__ orders,
                                                           ull* __restrict__ pan, ull* __restrict__ core) {
   __shared__ uint32_t ctr[LDS ? 2 * CMP_LDS_GROUPS : 1];
   if (LDS) {
-    for (uint32_t i = threadIdx.x; i < 2 * G; i += CMP_BLOCK) ctr[i] = 0;
+    for (uint32_t i = threadIdx.x; i < 2 * G; i += RG_BLOCK) ctr[i] = 0;
     __syncthreads();
   }
   const uint32_t p = blockIdx.y;
   const int* ord = orders + (uint64_t)p * G;
-  const uint64_t base = (uint64_t)blockIdx.x * (CMP_BLOCK * CV_COLS) + threadIdx.x;
+  const uint64_t base = (uint64_t)blockIdx.x * (RG_BLOCK * CV_COLS) + threadIdx.x;
   const uint64_t full = n / 64;                            // words whose 64 labels all exist
   ull o[CV_COLS], a[CV_COLS], x[CV_COLS];
   bool in[CV_COLS];
 #pragma unroll
   for (int c = 0; c < CV_COLS; ++c) {
-    const uint64_t w = base + (uint64_t)c * CMP_BLOCK;
+    const uint64_t w = base + (uint64_t)c * RG_BLOCK;
     in[c] = w < NW;
     o[c] = 0;
     a[c] = w < full ? ~0ull : (w == full ? (1ull << (n & 63)) - 1ull : 0ull);
   }
   const ull* row = T + (uint64_t)ord[0] * NW;
 #pragma unroll
-  for (int c = 0; c < CV_COLS; ++c) x[c] = in[c] ? row[base + (uint64_t)c * CMP_BLOCK] : 0ull;
+  for (int c = 0; c < CV_COLS; ++c) x[c] = in[c] ? row[base + (uint64_t)c * RG_BLOCK] : 0ull;
   for (uint32_t s = 0; s < G; ++s) {
     uint32_t v = 0;
 #pragma unroll
@@ -191,7 +186,7 @@ __global__ void __launch_bounds__(CMP_BLOCK) k_cmp_curves(const ull* __restrict_
     if (s + 1 < G) {                                       // the next row's loads fly during the reduction
       row = T + (uint64_t)ord[s + 1] * NW;
 #pragma unroll
-      for (int c = 0; c < CV_COLS; ++c) x[c] = in[c] ? row[base + (uint64_t)c * CMP_BLOCK] : 0ull;
+      for (int c = 0; c < CV_COLS; ++c) x[c] = in[c] ? row[base + (uint64_t)c * RG_BLOCK] : 0ull;
     }
 #pragma unroll
     for (int d = 32; d; d >>= 1) v += __shfl_xor(v, d);
@@ -201,23 +196,17 @@ __global__ void __launch_bounds__(CMP_BLOCK) k_cmp_curves(const ull* __restrict_
         if (vp) atomicAdd(&ctr[2 * s], vp);
         if (vc) atomicAdd(&ctr[2 * s + 1], vc);
       } else {
-        if (vp) CMP_ADD(pan + (uint64_t)p * G + s, (ull)vp);
-        if (vc) CMP_ADD(core + (uint64_t)p * G + s, (ull)vc);
+        if (vp) RG_ADD(pan + (uint64_t)p * G + s, (ull)vp);
+        if (vc) RG_ADD(core + (uint64_t)p * G + s, (ull)vc);
       }
     }
   }
   if (LDS) {
     __syncthreads();
-    for (uint32_t i = threadIdx.x; i < 2 * G; i += CMP_BLOCK)
-      if (ctr[i]) CMP_ADD(((i & 1) ? core : pan) + (uint64_t)p * G + (i >> 1), (ull)ctr[i]);
+    for (uint32_t i = threadIdx.x; i < 2 * G; i += RG_BLOCK)
+      if (ctr[i]) RG_ADD(((i & 1) ? core : pan) + (uint64_t)p * G + (i >> 1), (ull)ctr[i]);
   }
 }
-
-#define CMP_LAUNCH(kern, grid, ...)                                                      \
-  do {                                                                                   \
-    hipLaunchKernelGGL(kern, grid, dim3(CMP_BLOCK), 0, c.stream, __VA_ARGS__);           \
-    PG_HIP(hipGetLastError());                                                           \
-  } while (0)
 
 void freq_compare(Ctx& c, const uint64_t* h_bits, uint64_t n, uint32_t G, const int32_t* orders, uint32_t P) {
   // ---- arguments: everything refused here leaves the previous result in place
@@ -278,7 +267,7 @@ void freq_compare(Ctx& c, const uint64_t* h_bits, uint64_t n, uint32_t G, const 
     const unsigned cus = (unsigned)std::max(1, c.n_cu);
     // ---- a. transpose
     const uint64_t items = (NW + TR_WORDS - 1) / TR_WORDS * W;
-    CMP_LAUNCH(k_cmp_transpose, dim3((unsigned)std::min<uint64_t>(items, 64u * cus)), bits, n, W, G, NW, T);
+    RG_LAUNCH(k_cmp_transpose, dim3((unsigned)std::min<uint64_t>(items, 64u * cus)), bits, n, W, G, NW, T);
     // ---- b. shared.  Words per block: PG_TUNE_CMP_CHUNK, or by default what
     // gives about four blocks per compute unit over the upper tile triangle,
     // a multiple of SH_KT and at least 8 steps of it (a block's flush is up
@@ -293,23 +282,23 @@ void freq_compare(Ctx& c, const uint64_t* h_bits, uint64_t n, uint32_t G, const 
     cw = std::max<uint64_t>(cw, ((uint64_t)NW * nU + (1ull << 30) - 1) >> 30);      // (the grid stays below 2^31)
     cw = std::min<uint64_t>(cw, CMP_MAX_CHUNK);
     const uint64_t nchunk = (NW + cw - 1) / cw;
-    CMP_LAUNCH(k_cmp_shared, dim3((unsigned)(nchunk * nU)), T, NW, G, nT, nU, cw, shared.as<ull>());
-    if (nT > 1) CMP_LAUNCH(k_cmp_mirror, dim3(grid_for((uint64_t)G * G, CMP_BLOCK, 8192)), shared.as<ull>(), G);
+    RG_LAUNCH(k_cmp_shared, dim3((unsigned)(nchunk * nU)), T, NW, G, nT, nU, cw, shared.as<ull>());
+    if (nT > 1) RG_LAUNCH(k_cmp_mirror, dim3(grid_for((uint64_t)G * G, RG_BLOCK, 8192)), shared.as<ull>(), G);
     // ---- c. curves
     if (P) {
       ord.reserve(4 * (size_t)P * G);
       PG_HIP(hipMemcpyAsync(ord.p, orders, 4 * (size_t)P * G, hipMemcpyHostToDevice, c.stream));
       ull* pan = curve.as<ull>();
       ull* core = pan + (size_t)P * G;
-      const unsigned gx = (unsigned)((NW + CMP_BLOCK * CV_COLS - 1) / (CMP_BLOCK * CV_COLS));
+      const unsigned gx = (unsigned)((NW + RG_BLOCK * CV_COLS - 1) / (RG_BLOCK * CV_COLS));
       // (the grid's y is at most 65535: orders in slices)
       for (uint32_t p0 = 0; p0 < P; p0 += 65535u) {
         const unsigned gy = std::min<uint32_t>(65535u, P - p0);
         const int* o = ord.as<int>() + (size_t)p0 * G;
         if (c.cmp_form == 0 && G <= CMP_LDS_GROUPS)
-          CMP_LAUNCH(k_cmp_curves<true>, dim3(gx, gy), T, NW, n, G, o, pan + (size_t)p0 * G, core + (size_t)p0 * G);
+          RG_LAUNCH(k_cmp_curves<true>, dim3(gx, gy), T, NW, n, G, o, pan + (size_t)p0 * G, core + (size_t)p0 * G);
         else
-          CMP_LAUNCH(k_cmp_curves<false>, dim3(gx, gy), T, NW, n, G, o, pan + (size_t)p0 * G, core + (size_t)p0 * G);
+          RG_LAUNCH(k_cmp_curves<false>, dim3(gx, gy), T, NW, n, G, o, pan + (size_t)p0 * G, core + (size_t)p0 * G);
       }
     }
   }
@@ -322,12 +311,8 @@ void freq_compare(Ctx& c, const uint64_t* h_bits, uint64_t n, uint32_t G, const 
   c.cmp_ready = true;
 }
 
-static void cmp_need(const Ctx& c, const char* what) {
-  if (!c.cmp_ready) throw Error(-22, std::string(what) + ": no comparison (call pg_freq_compare first)");
-}
-
 void freq_shared(Ctx& c, uint64_t* shared, uint64_t cap) {
-  cmp_need(c, "pg_freq_shared");
+  need(c.cmp_ready, "pg_freq_shared", NEED_COMPARE);
   const uint64_t cells = (uint64_t)c.cmp_groups * c.cmp_groups;
   if (cap < cells) throw Error(-34, "pg_freq_shared: buffer too small");
   if (!cells || !shared) return;
@@ -336,7 +321,7 @@ void freq_shared(Ctx& c, uint64_t* shared, uint64_t cap) {
 }
 
 void freq_curve(Ctx& c, uint64_t* pan, uint64_t* core, uint64_t cap) {
-  cmp_need(c, "pg_freq_curve");
+  need(c.cmp_ready, "pg_freq_curve", NEED_COMPARE);
   const uint64_t cells = (uint64_t)c.cmp_orders * c.cmp_groups;
   if (cap < cells) throw Error(-34, "pg_freq_curve: buffer too small");
   if (!cells) return;

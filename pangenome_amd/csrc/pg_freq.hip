@@ -8,7 +8,8 @@
 // genome.  Tables are dense in the label (L = 1 + the largest used label).
 //
 // Steps, each its own launch on c.stream (no hand-shake inside a kernel):
-//   a. k_fr_scan    the largest used label, the used and the skipped rows
+//   a. k_row_scan   the largest used label, the used and the skipped rows
+//                   (the front end of every row pass: pg_region.h, pg_region.hip)
 //   b. k_fr_accum   one streaming pass over the rows into the dense per-label
 //                   arrays with no-return 64-bit add / min / max / or atomics
 //                   at agent scope
@@ -28,7 +29,7 @@
 // reduces their values across those lanes, and one lane issues the atomics -
 // five per wave and label instead of five per row.  Rows of one record are
 // adjacent in print order, so the presence word is one OR per wave, label and
-// genome.  Labels held by fewer than FR_AGG_MIN lanes of the wave are left to
+// genome.  Labels held by fewer than RG_AGG_MIN lanes of the wave are left to
 // their lanes.  PG_TUNE_FREQ_FORM 1 keeps the plain form (every lane its own
 // atomics) for comparison.
 //
@@ -37,167 +38,66 @@
 #include <cstring>
 #include <limits>
 
-#include "pg_internal.h"
-#include "pg_prim.h"
+#include "pg_region.h"
 
 namespace pg {
 
-typedef unsigned long long ull;
-
-#define FR_BLOCK 256
 #define FR_LDS_GROUPS 1024u        // k_fr_groups: 4 counters per genome in LDS up to here (32 KiB)
 #define FR_LDS_BINS 2048u          // k_fr_spectrum: 2 counters per bin in LDS up to here (32 KiB)
 
-#define FR_LOOP(i, n) \
-  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < (n); i += (uint64_t)gridDim.x * blockDim.x)
-
-#define FR_ADD(p, v) (void)__hip_atomic_fetch_add((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#define FR_OR(p, v) (void)__hip_atomic_fetch_or((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#define FR_MIN(p, v) (void)__hip_atomic_fetch_min((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#define FR_MAX(p, v) (void)__hip_atomic_fetch_max((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-
-// One tile of FR_BLOCK rows (40 bytes each) through LDS: the block reads the
-// tile's 5 x FR_BLOCK words as contiguous 8-byte loads (a wave: 512 contiguous
-// bytes per load) and every thread then takes its own row's five words.
-// Called by every thread of the block (two barriers); `have` = the thread has a row.
-struct Row {
-  long long rec, start, end, strand, label;
-};
-__device__ __forceinline__ bool fr_load_tile(const long long* __restrict__ rows, uint64_t n, uint64_t tile,
-                                             long long* lds, Row& r) {
-  const uint64_t base = tile * FR_BLOCK;                   // first row of the tile
-  const uint64_t nw = 5 * (n - base < FR_BLOCK ? n - base : (uint64_t)FR_BLOCK);
-  __syncthreads();                                         // (the previous tile's readers are done)
-#pragma unroll
-  for (int k = 0; k < 5; ++k) {
-    const uint32_t w = k * FR_BLOCK + threadIdx.x;
-    if (w < nw) lds[w] = rows[5 * base + w];
-  }
-  __syncthreads();
-  const bool have = base + threadIdx.x < n;
-  if (have) {
-    const long long* p = lds + 5 * threadIdx.x;
-    r.rec = p[0]; r.start = p[1]; r.end = p[2]; r.strand = p[3]; r.label = p[4];
-  }
-  return have;
-}
-__device__ __forceinline__ ull fr_len(const Row& r) {
-  return r.end >= r.start ? (ull)r.end - (ull)r.start : (ull)r.start - (ull)r.end;
-}
-__device__ __forceinline__ ull fr_readlane64(ull v, int lane) {
-  const uint32_t lo = __builtin_amdgcn_readlane((int)(uint32_t)v, lane);
-  const uint32_t hi = __builtin_amdgcn_readlane((int)(uint32_t)(v >> 32), lane);
-  return ((ull)hi << 32) | lo;
-}
-__device__ __forceinline__ ull fr_wave_sum(ull v) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ ull fr_wave_min(ull v) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) { const ull w = __shfl_xor(v, o); v = w < v ? w : v; }
-  return v;
-}
-__device__ __forceinline__ ull fr_wave_max(ull v) {
-#pragma unroll
-  for (int o = 32; o; o >>= 1) { const ull w = __shfl_xor(v, o); v = w > v ? w : v; }
-  return v;
-}
-
-// ------------------------------------------------------------ a. scan
-// out[0] = 1 + the largest used label (0: none), out[1] = used rows, out[2] = skipped rows
-__global__ void __launch_bounds__(FR_BLOCK) k_fr_scan(const long long* __restrict__ rows, uint64_t n,
-                                                      const int* __restrict__ rec_group, ull* __restrict__ out) {
-  __shared__ long long lds[5 * FR_BLOCK];
-  const uint64_t ntiles = (n + FR_BLOCK - 1) / FR_BLOCK;
-  ull top = 0, used = 0, skipped = 0;
-  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    Row r;
-    if (fr_load_tile(rows, n, t, lds, r)) {
-      const bool u = r.label >= 0 && rec_group[r.rec] >= 0;
-      used += u;
-      skipped += !u;
-      if (u && (ull)r.label + 1 > top) top = (ull)r.label + 1;
-    }
-  }
-  top = fr_wave_max(top);
-  used = fr_wave_sum(used);
-  skipped = fr_wave_sum(skipped);
-  if ((threadIdx.x & 63) == 0) {
-    if (top) FR_MAX(out, top);
-    if (used) FR_ADD(out + 1, used);
-    if (skipped) FR_ADD(out + 2, skipped);
-  }
-}
-
 // ------------------------------------------------------------ b. accumulate
 __global__ void k_fr_fill(ull* __restrict__ p, uint64_t n, ull v) {
-  FR_LOOP(i, n) p[i] = v;
+  RG_LOOP(i, n) p[i] = v;
 }
 
 // a lane's own six atomics (the plain form, and the rows the aggregated form leaves to it)
 __device__ __forceinline__ void fr_row_atomics(ull lab, ull len, bool plus, int g, uint32_t W, ull* d_rows,
                                                ull* d_plus, ull* d_bp, ull* d_min, ull* d_max, ull* d_bits) {
-  FR_ADD(d_rows + lab, 1ull);
-  if (plus) FR_ADD(d_plus + lab, 1ull);
-  FR_ADD(d_bp + lab, len);
-  FR_MIN(d_min + lab, len);
-  FR_MAX(d_max + lab, len);
-  FR_OR(d_bits + lab * W + ((uint32_t)g >> 6), 1ull << (g & 63));
+  RG_ADD(d_rows + lab, 1ull);
+  if (plus) RG_ADD(d_plus + lab, 1ull);
+  RG_ADD(d_bp + lab, len);
+  RG_MIN(d_min + lab, len);
+  RG_MAX(d_max + lab, len);
+  RG_OR(d_bits + lab * W + ((uint32_t)g >> 6), 1ull << (g & 63));
 }
 
 // PLAIN: every lane issues its own atomics.  Otherwise the wave takes the
-// label of its first unserved lane and ballots the lanes that share it; a
-// label held by FR_AGG_MIN lanes or more is reduced across them and one lane
-// issues its atomics, a label held by fewer is left to its lanes, which issue
-// theirs together once the wave has gone through its labels (one lane per
-// atomic instruction costs more than it saves: a wave of 64 labels would issue
-// 384 instructions of one lane instead of 6 of 64).
-#define FR_AGG_MIN 4
+// label of its first unserved lane and ballots the lanes that share it
+// (rg_by_label); a label held by RG_AGG_MIN lanes or more is reduced across
+// them and one lane issues its atomics, a label held by fewer is left to its
+// lanes, which issue theirs together once the wave has gone through its labels
+// (one lane per atomic instruction costs more than it saves: a wave of 64
+// labels would issue 384 instructions of one lane instead of 6 of 64).
 template <bool PLAIN>
-__global__ void __launch_bounds__(FR_BLOCK) k_fr_accum(const long long* __restrict__ rows, uint64_t n,
+__global__ void __launch_bounds__(RG_BLOCK) k_fr_accum(const long long* __restrict__ rows, uint64_t n,
                                                        const int* __restrict__ rec_group, uint32_t W,
                                                        ull* d_rows, ull* d_plus, ull* d_bp, ull* d_min, ull* d_max,
                                                        ull* d_bits) {
-  __shared__ long long lds[5 * FR_BLOCK];
-  const uint64_t ntiles = (n + FR_BLOCK - 1) / FR_BLOCK;
+  __shared__ long long lds[RG_TILE_WORDS(false)];
+  const uint64_t ntiles = (n + RG_BLOCK - 1) / RG_BLOCK;
   for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    Row r;
-    const bool have = fr_load_tile(rows, n, t, lds, r);
-    int g = -1;
-    if (have && r.label >= 0) g = rec_group[r.rec];
-    bool todo = g >= 0;
+    RgRow r;
+    const bool todo = rg_load_tile(rows, n, t, lds, r) && rs_used(r, rec_group);
+    const int g = todo ? rec_group[r.rec] : -1;
     const ull lab = todo ? (ull)r.label : 0ull;
-    const ull len = todo ? fr_len(r) : 0ull;
+    const ull len = todo ? rg_len(r) : 0ull;
     const bool plus = todo && r.strand == 1;
     bool own = todo;                                       // this lane issues its own atomics
     if (!PLAIN) {
-      // every lane of the wave runs the loops (their conditions are ballots)
+      // every lane of the wave runs the loop (its conditions are ballots) and calls the callback, so the
+      // ballots and reductions inside the callback are whole-wave too
       const int lane = threadIdx.x & 63;
-      own = false;
-      for (;;) {
-        const ull open = __ballot(todo);
-        if (!open) break;
-        const int lead = __ffsll(open) - 1;
-        const ull lab0 = fr_readlane64(lab, lead);
-        const bool mine = todo && lab == lab0;
-        const ull m = __ballot(mine);
-        todo = todo && !mine;
-        if (__popcll(m) < FR_AGG_MIN) {
-          own = own || mine;
-          continue;
-        }
+      own = rg_by_label(todo, lab, [&](ull lab0, bool mine, ull cnt, bool leader) {
         const ull mp = __ballot(mine && plus);
-        const ull sum = fr_wave_sum(mine ? len : 0ull);
-        const ull lo = fr_wave_min(mine ? len : ~0ull);
-        const ull hi = fr_wave_max(mine ? len : 0ull);
-        if (lane == lead) {
-          FR_ADD(d_rows + lab0, (ull)__popcll(m));
-          if (mp) FR_ADD(d_plus + lab0, (ull)__popcll(mp));
-          FR_ADD(d_bp + lab0, sum);
-          FR_MIN(d_min + lab0, lo);
-          FR_MAX(d_max + lab0, hi);
+        const ull sum = rg_wave_sum(mine ? len : 0ull);
+        const ull lo = rg_wave_min(mine ? len : ~0ull);
+        const ull hi = rg_wave_max(mine ? len : 0ull);
+        if (leader) {
+          RG_ADD(d_rows + lab0, cnt);
+          if (mp) RG_ADD(d_plus + lab0, (ull)__popcll(mp));
+          RG_ADD(d_bp + lab0, sum);
+          RG_MIN(d_min + lab0, lo);
+          RG_MAX(d_max + lab0, hi);
         }
         // the presence set: one OR per genome among these lanes (rows of a record are adjacent)
         bool gtodo = mine;
@@ -206,10 +106,10 @@ __global__ void __launch_bounds__(FR_BLOCK) k_fr_accum(const long long* __restri
           if (!gopen) break;
           const int glead = __ffsll(gopen) - 1;
           const int g0 = __builtin_amdgcn_readlane(g, glead);
-          if (lane == glead) FR_OR(d_bits + lab0 * W + ((uint32_t)g0 >> 6), 1ull << (g0 & 63));
+          if (lane == glead) RG_OR(d_bits + lab0 * W + ((uint32_t)g0 >> 6), 1ull << (g0 & 63));
           gtodo = gtodo && g != g0;
         }
-      }
+      });
     }
     if (own) fr_row_atomics(lab, len, plus, g, W, d_rows, d_plus, d_bp, d_min, d_max, d_bits);
   }
@@ -218,7 +118,7 @@ __global__ void __launch_bounds__(FR_BLOCK) k_fr_accum(const long long* __restri
 // ------------------------------------------------------------ c, d. table
 __global__ void k_fr_dense(const ull* __restrict__ d_rows, const ull* __restrict__ d_bits, uint64_t L, uint32_t W,
                            uint8_t* __restrict__ flag, uint32_t* __restrict__ ngen) {
-  FR_LOOP(l, L) {
+  RG_LOOP(l, L) {
     uint32_t c = 0;
     for (uint32_t w = 0; w < W; ++w) c += __popcll(d_bits[l * W + w]);
     ngen[l] = c;
@@ -232,7 +132,7 @@ __global__ void k_fr_gather(const long long* __restrict__ labs, uint64_t nt, uin
                             const uint32_t* __restrict__ d_ngen, ull* __restrict__ t_rows, ull* __restrict__ t_plus,
                             ull* __restrict__ t_bp, ull* __restrict__ t_min, ull* __restrict__ t_max,
                             ull* __restrict__ t_bits, uint32_t* __restrict__ t_ngen) {
-  FR_LOOP(i, nt) {
+  RG_LOOP(i, nt) {
     const uint64_t l = (uint64_t)labs[i];
     t_rows[i] = d_rows[l];
     t_plus[i] = d_plus[l];
@@ -247,7 +147,7 @@ __global__ void k_fr_gather(const long long* __restrict__ labs, uint64_t nt, uin
 // ------------------------------------------------------------ e. spectrum
 // spec[0..G] = labels by number of genomes, spec[G+1..2G+1] = their bases
 template <bool LDS>
-__global__ void __launch_bounds__(FR_BLOCK) k_fr_spectrum(const uint32_t* __restrict__ t_ngen,
+__global__ void __launch_bounds__(RG_BLOCK) k_fr_spectrum(const uint32_t* __restrict__ t_ngen,
                                                           const ull* __restrict__ t_bp, uint64_t nt, uint32_t G,
                                                           ull* __restrict__ spec) {
   __shared__ ull bins[LDS ? 2 * FR_LDS_BINS : 1];
@@ -256,41 +156,40 @@ __global__ void __launch_bounds__(FR_BLOCK) k_fr_spectrum(const uint32_t* __rest
     for (uint32_t i = threadIdx.x; i < 2 * nb; i += blockDim.x) bins[i] = 0;
     __syncthreads();
   }
-  FR_LOOP(i, nt) {
+  RG_LOOP(i, nt) {
     const uint32_t g = t_ngen[i];
     if (LDS) {
       atomicAdd(&bins[g], 1ull);
       atomicAdd(&bins[nb + g], t_bp[i]);
     } else {
-      FR_ADD(spec + g, 1ull);
-      FR_ADD(spec + nb + g, t_bp[i]);
+      RG_ADD(spec + g, 1ull);
+      RG_ADD(spec + nb + g, t_bp[i]);
     }
   }
   if (LDS) {
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < 2 * nb; i += blockDim.x)
-      if (bins[i]) FR_ADD(spec + i, bins[i]);
+      if (bins[i]) RG_ADD(spec + i, bins[i]);
   }
 }
 
 // ------------------------------------------------------------ f. per genome
 // grp: [5][G] = rows, bases, core, shell, unique (shell by k_fr_shell)
 template <bool LDS>
-__global__ void __launch_bounds__(FR_BLOCK) k_fr_groups(const long long* __restrict__ rows, uint64_t n,
+__global__ void __launch_bounds__(RG_BLOCK) k_fr_groups(const long long* __restrict__ rows, uint64_t n,
                                                         const int* __restrict__ rec_group,
                                                         const uint32_t* __restrict__ d_ngen, uint32_t G,
                                                         ull* __restrict__ grp) {
-  __shared__ long long lds[5 * FR_BLOCK];
+  __shared__ long long lds[RG_TILE_WORDS(false)];
   __shared__ ull acc[LDS ? 4 * FR_LDS_GROUPS : 1];
   if (LDS)
-    for (uint32_t i = threadIdx.x; i < 4 * G; i += blockDim.x) acc[i] = 0;   // (fr_load_tile's barrier orders this)
-  const uint64_t ntiles = (n + FR_BLOCK - 1) / FR_BLOCK;
+    for (uint32_t i = threadIdx.x; i < 4 * G; i += blockDim.x) acc[i] = 0;   // (rg_load_tile's barrier orders this)
+  const uint64_t ntiles = (n + RG_BLOCK - 1) / RG_BLOCK;
   for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    Row r;
-    if (!fr_load_tile(rows, n, t, lds, r) || r.label < 0) continue;
+    RgRow r;
+    if (!rg_load_tile(rows, n, t, lds, r) || !rs_used(r, rec_group)) continue;
     const int g = rec_group[r.rec];
-    if (g < 0) continue;
-    const ull len = fr_len(r);
+    const ull len = rg_len(r);
     const uint32_t ng = d_ngen[r.label];
     const int cls = ng == G ? 2 : (ng == 1 ? 3 : -1);      // (one genome in all: everything is core)
     if (LDS) {
@@ -298,21 +197,21 @@ __global__ void __launch_bounds__(FR_BLOCK) k_fr_groups(const long long* __restr
       atomicAdd(&acc[G + g], len);
       if (cls >= 0) atomicAdd(&acc[cls * G + g], len);
     } else {
-      FR_ADD(grp + g, 1ull);
-      FR_ADD(grp + G + g, len);
-      if (cls >= 0) FR_ADD(grp + (uint64_t)(cls == 2 ? 2 : 4) * G + g, len);
+      RG_ADD(grp + g, 1ull);
+      RG_ADD(grp + G + g, len);
+      if (cls >= 0) RG_ADD(grp + (uint64_t)(cls == 2 ? 2 : 4) * G + g, len);
     }
   }
   if (LDS) {
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < 4 * G; i += blockDim.x) {
       const uint32_t col = i / G, g = i - col * G;         // LDS columns: rows, bases, core, unique
-      if (acc[i]) FR_ADD(grp + (uint64_t)(col == 3 ? 4 : col) * G + g, acc[i]);
+      if (acc[i]) RG_ADD(grp + (uint64_t)(col == 3 ? 4 : col) * G + g, acc[i]);
     }
   }
 }
 __global__ void k_fr_shell(ull* __restrict__ grp, uint32_t G) {
-  FR_LOOP(g, G) grp[3ull * G + g] = grp[1ull * G + g] - grp[2ull * G + g] - grp[4ull * G + g];
+  RG_LOOP(g, G) grp[3ull * G + g] = grp[1ull * G + g] - grp[2ull * G + g] - grp[4ull * G + g];
 }
 
 // ------------------------------------------------------------ g. text
@@ -321,7 +220,7 @@ __global__ void k_fr_len(const long long* __restrict__ labs, const uint32_t* __r
                          const ull* __restrict__ t_rows, const ull* __restrict__ t_plus, const ull* __restrict__ t_bp,
                          const ull* __restrict__ t_min, const ull* __restrict__ t_max, uint64_t nt,
                          ull* __restrict__ len) {
-  FR_LOOP(i, nt)
+  RG_LOOP(i, nt)
     len[i] = ndig((ull)labs[i]) + ndig(t_ngen[i]) + ndig(t_rows[i]) + ndig(t_plus[i]) + ndig(t_bp[i]) +
              ndig(t_min[i]) + ndig(t_max[i]) + 7;
 }
@@ -329,7 +228,7 @@ __global__ void k_fr_write(const long long* __restrict__ labs, const uint32_t* _
                            const ull* __restrict__ t_rows, const ull* __restrict__ t_plus,
                            const ull* __restrict__ t_bp, const ull* __restrict__ t_min, const ull* __restrict__ t_max,
                            uint64_t nt, const ull* __restrict__ off, char* __restrict__ out) {
-  FR_LOOP(i, nt) {
+  RG_LOOP(i, nt) {
     char* o = out + off[i];
     o = put_dec(o, (ull)labs[i]); *o++ = '\t';
     o = put_dec(o, t_ngen[i]); *o++ = '\t';
@@ -340,12 +239,6 @@ __global__ void k_fr_write(const long long* __restrict__ labs, const uint32_t* _
     o = put_dec(o, t_max[i]); *o = '\n';
   }
 }
-
-#define FR_LAUNCH(kern, grid, ...)                                                       \
-  do {                                                                                   \
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(FR_BLOCK), 0, c.stream, __VA_ARGS__);      \
-    PG_HIP(hipGetLastError());                                                           \
-  } while (0)
 
 // the table's columns inside c.fr_tab (nt entries, W presence words each)
 struct FrCols {
@@ -368,53 +261,19 @@ struct FrCols {
 void freq(Ctx& c, const int64_t* h_rows5, uint64_t n_rows, const int32_t* rec_group, uint64_t n_records,
           uint32_t G, uint64_t* n_labels, uint64_t* n_used, uint64_t* n_skipped) {
   // ---- arguments: everything refused here leaves the previous result in place
-  if (!rec_group) throw Error(-22, "pg_freq: rec_group is NULL");
-  if (!h_rows5) {
-    if (!c.rows_ready) throw Error(-22, "pg_freq: no row pass (call pg_rows first, or pass rows)");
-    if (n_records != c.n_records)
-      throw Error(-22, "pg_freq: " + std::to_string(n_records) + " records, the context has " +
-                           std::to_string(c.n_records));
-    n_rows = c.n_rows;
-  }
-  for (uint64_t r = 0; r < n_records; ++r)
-    if (rec_group[r] < -1 || (int64_t)rec_group[r] >= (int64_t)G)
-      throw Error(-22, "pg_freq: rec_group[" + std::to_string(r) + "] = " + std::to_string(rec_group[r]) +
-                           " is outside [-1, " + std::to_string(G) + ")");
-  if (h_rows5)
-    for (uint64_t i = 0; i < n_rows; ++i)
-      if (h_rows5[5 * i] < 0 || (uint64_t)h_rows5[5 * i] >= n_records)
-        throw Error(-22, "pg_freq: row " + std::to_string(i) + " names record " + std::to_string(h_rows5[5 * i]) +
-                             " of " + std::to_string(n_records));
-  if (G == 0 && n_rows) throw Error(-22, "pg_freq: n_groups is 0 with rows");
-
+  const RowInput in = row_input(c, "pg_freq", h_rows5, n_rows, rec_group, n_records, G, false);
+  n_rows = in.n;
   const uint32_t W = (uint32_t)(((uint64_t)G + 63) / 64);
-  const unsigned grid_rows = grid_for((n_rows + FR_BLOCK - 1) / FR_BLOCK, 1, 8u * (unsigned)std::max(1, c.n_cu));
-  DevBuf up, grpmap, ctr;
-  const long long* rows = c.rows_buf.as<long long>();
-  if (h_rows5) {
-    up.reserve(40 * (n_rows + 1));
-    if (n_rows) PG_HIP(hipMemcpyAsync(up.p, h_rows5, 40 * n_rows, hipMemcpyHostToDevice, c.stream));
-    rows = up.as<long long>();
-  }
-  grpmap.reserve(4 * (n_records + 1));
-  if (n_records) PG_HIP(hipMemcpyAsync(grpmap.p, rec_group, 4 * n_records, hipMemcpyHostToDevice, c.stream));
-  const int* d_group = grpmap.as<int>();
+  const unsigned grid_rows = in.grid_rows;
+  const long long* rows = in.rows;
+  const int* d_group = in.group;
 
   // ---- a. the dense size, found before anything is allocated or replaced
-  ull h3[3] = {0, 0, 0};
-  if (n_rows) {
-    ctr.reserve(32);
-    PG_HIP(hipMemsetAsync(ctr.p, 0, 24, c.stream));
-    FR_LAUNCH(k_fr_scan, grid_rows, rows, n_rows, d_group, ctr.as<ull>());
-    PG_HIP(hipMemcpyAsync(h3, ctr.p, 24, hipMemcpyDeviceToHost, c.stream));
-    c.sync();
-  }
-  const uint64_t L = h3[0];
-  if (L > (1ull << 31))
-    throw Error(-34, "pg_freq: the largest used label is " + std::to_string(L - 1) + ": the dense tables take labels below 2^31");
+  const RowScan sc = row_scan(c, "pg_freq", in, nullptr, nullptr);
+  const uint64_t L = sc.L;
 
   // ---- b, c. dense per-label arrays: rows, plus, bases, min, max, [W] presence words
-  DevBuf dense, dflag, dngen, labs, cntb, tab, spec, grp, tlen, toff, text;
+  DevBuf dense, dflag, dngen, labs, tab, spec, grp, tlen, toff, text;
   uint64_t nt = 0;
   spec.reserve(16 * ((size_t)G + 1));
   grp.reserve(40 * (size_t)G + 16);
@@ -425,42 +284,33 @@ void freq(Ctx& c, const int64_t* h_rows5, uint64_t n_rows, const int32_t* rec_gr
     ull* d_rows = dense.as<ull>();
     ull *d_plus = d_rows + L, *d_bp = d_plus + L, *d_min = d_bp + L, *d_max = d_min + L, *d_bits = d_max + L;
     PG_HIP(hipMemsetAsync(dense.p, 0, 8 * (5 + (size_t)W) * L, c.stream));
-    FR_LAUNCH(k_fr_fill, grid_for(L, FR_BLOCK, 8192), d_min, L, ~0ull);
+    RG_LAUNCH(k_fr_fill, grid_for(L, RG_BLOCK, 8192), d_min, L, ~0ull);
     if (c.freq_form == 1)
-      FR_LAUNCH(k_fr_accum<true>, grid_rows, rows, n_rows, d_group, W, d_rows, d_plus, d_bp, d_min, d_max, d_bits);
+      RG_LAUNCH(k_fr_accum<true>, grid_rows, rows, n_rows, d_group, W, d_rows, d_plus, d_bp, d_min, d_max, d_bits);
     else
-      FR_LAUNCH(k_fr_accum<false>, grid_rows, rows, n_rows, d_group, W, d_rows, d_plus, d_bp, d_min, d_max, d_bits);
+      RG_LAUNCH(k_fr_accum<false>, grid_rows, rows, n_rows, d_group, W, d_rows, d_plus, d_bp, d_min, d_max, d_bits);
     dflag.reserve(L + 16);
     dngen.reserve(4 * L + 16);
-    FR_LAUNCH(k_fr_dense, grid_for(L, FR_BLOCK, 8192), d_rows, d_bits, L, W, dflag.as<uint8_t>(), dngen.as<uint32_t>());
-    // ---- d. the labels seen, ascending (a counting iterator through rocprim::select)
-    labs.reserve(8 * (L + 1));
-    cntb.reserve(16);
-    with_temp(c, [&](void* tmp, size_t& bytes) {
-      return rocprim::select(tmp, bytes, rocprim::counting_iterator<long long>(0), dflag.as<uint8_t>(),
-                             labs.as<long long>(), cntb.as<ull>(), (size_t)L, c.stream);
-    });
-    ull h = 0;
-    PG_HIP(hipMemcpyAsync(&h, cntb.p, 8, hipMemcpyDeviceToHost, c.stream));
-    c.sync();
-    nt = h;
+    RG_LAUNCH(k_fr_dense, grid_for(L, RG_BLOCK, 8192), d_rows, d_bits, L, W, dflag.as<uint8_t>(), dngen.as<uint32_t>());
+    // ---- d. the labels seen, ascending
+    nt = labels_seen(c, dflag.as<uint8_t>(), L, labs);
     tab.reserve(FrCols::bytes(nt, W));
     FrCols T(tab, nt, W);
     PG_HIP(hipMemcpyAsync(T.label, labs.p, 8 * nt, hipMemcpyDeviceToDevice, c.stream));
-    FR_LAUNCH(k_fr_gather, grid_for(nt, FR_BLOCK, 8192), T.label, nt, W, d_rows, d_plus, d_bp, d_min, d_max, d_bits,
+    RG_LAUNCH(k_fr_gather, grid_for(nt, RG_BLOCK, 8192), T.label, nt, W, d_rows, d_plus, d_bp, d_min, d_max, d_bits,
               dngen.as<uint32_t>(), T.rows, T.plus, T.bp, T.mn, T.mx, T.bits, T.ngen);
     // ---- e. spectrum
     if ((uint64_t)G + 1 <= FR_LDS_BINS)
-      FR_LAUNCH(k_fr_spectrum<true>, grid_for(nt, FR_BLOCK, 1024), T.ngen, T.bp, nt, G, spec.as<ull>());
+      RG_LAUNCH(k_fr_spectrum<true>, grid_for(nt, RG_BLOCK, 1024), T.ngen, T.bp, nt, G, spec.as<ull>());
     else
-      FR_LAUNCH(k_fr_spectrum<false>, grid_for(nt, FR_BLOCK, 8192), T.ngen, T.bp, nt, G, spec.as<ull>());
+      RG_LAUNCH(k_fr_spectrum<false>, grid_for(nt, RG_BLOCK, 8192), T.ngen, T.bp, nt, G, spec.as<ull>());
     // ---- f. per genome
     if (G <= FR_LDS_GROUPS)
-      FR_LAUNCH(k_fr_groups<true>, std::min(grid_rows, 2u * (unsigned)std::max(1, c.n_cu)), rows, n_rows, d_group,
+      RG_LAUNCH(k_fr_groups<true>, std::min(grid_rows, 2u * (unsigned)std::max(1, c.n_cu)), rows, n_rows, d_group,
                 dngen.as<uint32_t>(), G, grp.as<ull>());
     else
-      FR_LAUNCH(k_fr_groups<false>, grid_rows, rows, n_rows, d_group, dngen.as<uint32_t>(), G, grp.as<ull>());
-    FR_LAUNCH(k_fr_shell, grid_for(G, FR_BLOCK, 8192), grp.as<ull>(), G);
+      RG_LAUNCH(k_fr_groups<false>, grid_rows, rows, n_rows, d_group, dngen.as<uint32_t>(), G, grp.as<ull>());
+    RG_LAUNCH(k_fr_shell, grid_for(G, RG_BLOCK, 8192), grp.as<ull>(), G);
   } else {
     tab.reserve(FrCols::bytes(0, W));
   }
@@ -471,14 +321,14 @@ void freq(Ctx& c, const int64_t* h_rows5, uint64_t n_rows, const int32_t* rec_gr
   if (nt) {
     tlen.reserve(8 * (nt + 1));
     toff.reserve(8 * (nt + 1));
-    FR_LAUNCH(k_fr_len, grid_for(nt, FR_BLOCK, 8192), T.label, T.ngen, T.rows, T.plus, T.bp, T.mn, T.mx, nt,
+    RG_LAUNCH(k_fr_len, grid_for(nt, RG_BLOCK, 8192), T.label, T.ngen, T.rows, T.plus, T.bp, T.mn, T.mx, nt,
               tlen.as<ull>());
     body = excl_scan_total(c, tlen.as<ull>(), toff.as<ull>(), nt);
   }
   text.reserve(hdr + body + 16);
   PG_HIP(hipMemcpyAsync(text.p, FR_HEADER, hdr, hipMemcpyHostToDevice, c.stream));
   if (nt)
-    FR_LAUNCH(k_fr_write, grid_for(nt, FR_BLOCK, 8192), T.label, T.ngen, T.rows, T.plus, T.bp, T.mn, T.mx, nt,
+    RG_LAUNCH(k_fr_write, grid_for(nt, RG_BLOCK, 8192), T.label, T.ngen, T.rows, T.plus, T.bp, T.mn, T.mx, nt,
               toff.as<ull>(), text.as<char>() + hdr);
   c.sync();
   // ---- the new result replaces the previous one
@@ -493,37 +343,30 @@ void freq(Ctx& c, const int64_t* h_rows5, uint64_t n_rows, const int32_t* rec_gr
   c.fr_ready = true;
   c.cmp_ready = false;                                     // (a comparison described the old table)
   if (n_labels) *n_labels = nt;
-  if (n_used) *n_used = h3[1];
-  if (n_skipped) *n_skipped = h3[2];
-}
-
-static void fr_need(const Ctx& c, const char* what) {
-  if (!c.fr_ready) throw Error(-22, std::string(what) + ": no frequency table (call pg_freq first)");
+  if (n_used) *n_used = sc.used;
+  if (n_skipped) *n_skipped = sc.skipped;
 }
 
 void freq_export(Ctx& c, int64_t* label, uint32_t* n_genomes, uint64_t* n_rows, uint64_t* n_plus, uint64_t* total_bp,
                  uint64_t* min_len, uint64_t* max_len, uint64_t* bits, uint64_t cap) {
-  fr_need(c, "pg_freq_export");
+  need(c.fr_ready, "pg_freq_export", NEED_FREQ);
   const uint64_t nt = c.fr_n;
   if (cap < nt) throw Error(-34, "pg_freq_export: buffer too small");
   if (!nt) return;
   FrCols T(c.fr_tab, nt, c.fr_words);
-  auto get = [&](void* dst, const void* src, size_t bytes) {
-    if (dst && bytes) PG_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c.stream));
-  };
-  get(label, T.label, 8 * nt);
-  get(n_genomes, T.ngen, 4 * nt);
-  get(n_rows, T.rows, 8 * nt);
-  get(n_plus, T.plus, 8 * nt);
-  get(total_bp, T.bp, 8 * nt);
-  get(min_len, T.mn, 8 * nt);
-  get(max_len, T.mx, 8 * nt);
-  get(bits, T.bits, 8 * (size_t)c.fr_words * nt);
+  get(c, label, T.label, 8 * nt);
+  get(c, n_genomes, T.ngen, 4 * nt);
+  get(c, n_rows, T.rows, 8 * nt);
+  get(c, n_plus, T.plus, 8 * nt);
+  get(c, total_bp, T.bp, 8 * nt);
+  get(c, min_len, T.mn, 8 * nt);
+  get(c, max_len, T.mx, 8 * nt);
+  get(c, bits, T.bits, 8 * (size_t)c.fr_words * nt);
   c.sync();
 }
 
 void freq_spectrum(Ctx& c, uint64_t* labels_by_g, uint64_t* bp_by_g, uint64_t cap) {
-  fr_need(c, "pg_freq_spectrum");
+  need(c.fr_ready, "pg_freq_spectrum", NEED_FREQ);
   const uint64_t nb = (uint64_t)c.fr_groups + 1;
   if (cap < nb) throw Error(-34, "pg_freq_spectrum: buffer too small");
   if (labels_by_g) PG_HIP(hipMemcpyAsync(labels_by_g, c.fr_spec.p, 8 * nb, hipMemcpyDeviceToHost, c.stream));
@@ -533,7 +376,7 @@ void freq_spectrum(Ctx& c, uint64_t* labels_by_g, uint64_t* bp_by_g, uint64_t ca
 
 void freq_groups(Ctx& c, uint64_t* rows, uint64_t* bp_total, uint64_t* bp_core, uint64_t* bp_shell,
                  uint64_t* bp_unique, uint64_t cap) {
-  fr_need(c, "pg_freq_groups");
+  need(c.fr_ready, "pg_freq_groups", NEED_FREQ);
   const uint64_t G = c.fr_groups;
   if (cap < G) throw Error(-34, "pg_freq_groups: buffer too small");
   if (!G) return;
@@ -545,16 +388,8 @@ void freq_groups(Ctx& c, uint64_t* rows, uint64_t* bp_total, uint64_t* bp_core, 
 
 // the text of the last freq: its size (out null, fd < 0), copied into out, or written to descriptor fd
 uint64_t format_freq(Ctx& c, char* out, uint64_t cap, int fd) {
-  fr_need(c, fd >= 0 ? "pg_freq_format_fd" : "pg_freq_format");
-  if (!out && fd < 0) return c.fr_total;
-  if (out && cap < c.fr_total) throw Error(-34, "pg_freq_format: buffer too small");
-  if (out) {
-    PG_HIP(hipMemcpyAsync(out, c.fr_text.p, c.fr_total, hipMemcpyDeviceToHost, c.stream));
-    c.sync();
-  } else {
-    text_to_fd(c, c.fr_text.as<uint8_t>(), c.fr_total, fd, "pg_freq_format_fd");
-  }
-  return c.fr_total;
+  need(c.fr_ready, fd >= 0 ? "pg_freq_format_fd" : "pg_freq_format", NEED_FREQ);
+  return text_out(c, c.fr_text.p, c.fr_total, out, cap, fd, "pg_freq_format", "pg_freq_format_fd");
 }
 
 }  // namespace pg

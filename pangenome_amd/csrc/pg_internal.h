@@ -56,6 +56,7 @@ struct DevBuf {
   DevBuf() = default;
   DevBuf(const DevBuf&) = delete;
   DevBuf& operator=(const DevBuf&) = delete;
+  DevBuf(DevBuf&& o) noexcept { swap(o); }  // (a function may return the buffers it filled)
   ~DevBuf() { release(); }                // (function-local scratch buffers free themselves)
   void reserve(size_t bytes) {
     if (bytes <= cap) return;
@@ -472,7 +473,59 @@ void freq_compare(Ctx& c, const uint64_t* h_bits, uint64_t n_labels, uint32_t n_
 void freq_shared(Ctx& c, uint64_t* shared, uint64_t cap);
 void freq_curve(Ctx& c, uint64_t* pan, uint64_t* core, uint64_t cap);
 
-// pg_region.hip
+// pg_region.hip: the front end the passes over the region rows share (pg_freq, pg_region_graph,
+// pg_region_seqs; device side in pg_region.h)
+// The arguments of a row pass checked (`what`, the pass's pg_ name, begins every message: -22) and its
+// input on the device: the rows (h_rows5 NULL: the last row pass's, where they lie) and rec_group.
+// records_match_always: n_records must be the context's record count even with host rows (pg_region_seqs,
+// whose bases are the context's); otherwise only with the device rows, and host rows may come with
+// any n_records that covers them (pg_freq, pg_region_graph).  The difference is kept as it was found.
+struct RowInput {
+  DevBuf up, grpmap;              // own the uploads
+  const long long* rows;          // [n][5]
+  const int* group;               // [n_records]
+  uint64_t n;                     // rows
+  unsigned grid_rows;             // blocks of a pass over the row tiles
+};
+RowInput row_input(Ctx& c, const char* what, const int64_t* h_rows5, uint64_t n_rows, const int32_t* rec_group,
+                   uint64_t n_records, uint32_t n_groups, bool records_match_always);
+// One pass over the rows (k_row_scan): L = 1 + the largest used label (0: none), the used and the skipped
+// rows, names = 1 + the largest record of a used row.  rf (n + 1 bytes) non-null: the USED / HEAD flag byte
+// of every row, rf[n] = 0.  rec_len non-null: -22 if a used row reaches outside its record.  -34 if L > 2^31.
+struct RowScan {
+  uint64_t L, used, skipped, names;
+};
+RowScan row_scan(Ctx& c, const char* what, const RowInput& in, uint8_t* rf, const long long* rec_len);
+// the labels l < L with flag[l] set, ascending, into labs; returns their number
+uint64_t labels_seen(Ctx& c, const uint8_t* flag, uint64_t L, DevBuf& labs);
+// The end of a text call over `total` device bytes: their number alone (out null, fd < 0), or the text
+// copied into out (cap: its room; -34 in `what`'s name if too small) or written to descriptor fd.
+// text_wanted: the first two steps alone, for a text that is only made when it is wanted.
+bool text_wanted(uint64_t total, const char* out, uint64_t cap, int fd, const char* what);
+uint64_t text_out(Ctx& c, const void* d_text, uint64_t total, char* out, uint64_t cap, int fd, const char* what,
+                  const char* what_fd);
+// The record names of a text call checked (-22: fewer than the n_needed that `noun` need, offsets not
+// ascending, NULL) and uploaded: off [n_names + 1], then the bytes.
+struct DevNames {
+  DevBuf buf;
+  const long long* off;
+  const char* bytes;
+};
+DevNames names_upload(Ctx& c, const char* what, const char* names, const int64_t* name_off, uint64_t n_names,
+                      uint64_t n_needed, const char* noun);
+// the result a call reads is there, or -22 "<what>: <hint>"
+#define NEED_FREQ "no frequency table (call pg_freq first)"
+#define NEED_COMPARE "no comparison (call pg_freq_compare first)"
+#define NEED_GRAPH "no region graph (call pg_region_graph first)"
+#define NEED_SEQS "no region sequences (call pg_region_seqs first)"
+inline void need(bool ready, const char* what, const char* hint) {
+  if (!ready) throw Error(-22, std::string(what) + ": " + hint);
+}
+// an optional column of a result to the host, on c.stream
+inline void get(Ctx& c, void* dst, const void* src, size_t bytes) {
+  if (dst && bytes) PG_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c.stream));
+}
+
 // The region graph of rows (h_rows5 NULL: the last row pass) grouped by
 // rec_group: nodes, links and paths; replaces the context's previous graph
 // only when it succeeds.

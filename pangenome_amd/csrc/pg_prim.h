@@ -1,12 +1,32 @@
-// pg_prim.h — rocPRIM calls on the context's stream and scratch, and the
-// decimal text helpers, shared by the walk passes (pg_walk.hip) and the
-// clusterer (pg_cluster.hip).
+// pg_prim.h — what every pass after the build shares: the grid-stride loop,
+// the launch on the context's stream and the no-return agent-scope atomics;
+// rocPRIM calls on the context's stream and scratch; the decimal text helpers.
+// (What only the passes over the region rows share is in pg_region.h.)
 #pragma once
 #include <rocprim/rocprim.hpp>
 
 #include "pg_internal.h"
 
 namespace pg {
+
+typedef unsigned long long ull;
+
+#define RG_BLOCK 256
+
+#define RG_LOOP(i, n) \
+  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < (n); i += (uint64_t)gridDim.x * blockDim.x)
+
+#define RG_ADD(p, v) (void)__hip_atomic_fetch_add((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+#define RG_OR(p, v) (void)__hip_atomic_fetch_or((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+#define RG_MAX(p, v) (void)__hip_atomic_fetch_max((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+#define RG_MIN(p, v) (void)__hip_atomic_fetch_min((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+
+// grid: a block count or a dim3; `c` is the caller's context
+#define RG_LAUNCH(kern, grid, ...)                                                       \
+  do {                                                                                   \
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(RG_BLOCK), 0, c.stream, __VA_ARGS__);      \
+    PG_HIP(hipGetLastError());                                                           \
+  } while (0)
 
 template <class F>
 static void with_temp(Ctx& c, F&& f) {
@@ -23,8 +43,9 @@ static void sort_pairs(Ctx& c, const K* kin, K* kout, const V* vin, V* vout, uin
     return rocprim::radix_sort_pairs(tmp, bytes, kin, kout, vin, vout, (size_t)n, 0, end_bit, c.stream);
   });
 }
-template <class T>
-static uint64_t select_flagged(Ctx& c, const T* in, const uint8_t* flags, T* out, uint64_t n, DevBuf& cnt) {
+// out: the items of in[0 .. n) (a pointer or any iterator) whose flag byte is set, in order; returns their number
+template <class In, class T>
+static uint64_t select_flagged(Ctx& c, In in, const uint8_t* flags, T* out, uint64_t n, DevBuf& cnt) {
   cnt.reserve(16);
   with_temp(c, [&](void* tmp, size_t& bytes) {
     return rocprim::select(tmp, bytes, in, flags, out, cnt.as<unsigned long long>(), (size_t)n, c.stream);

@@ -1,57 +1,65 @@
-// pg_region.h — what the passes over the region rows share (pg_region.hip, the
-// region graph; pg_regionseq.hip, the region sequences): a tile of rows
-// through LDS, the wave reductions, the lanes of a wave grouped by label, the
-// signed decimals and the node table of the graph.
+// pg_region.h — the device side of what the passes over the region rows share
+// (pg_freq.hip, the frequency table; pg_region.hip, the region graph;
+// pg_regionseq.hip, the region sequences): the row and the rule for a used one
+// (RgRow, rs_used), a tile of rows through LDS with or without the row before
+// it (rg_load_tile), the wave reductions, the lanes of a wave grouped by label
+// (rg_by_label), the signed decimals and the node table of the graph.  The
+// loop, launch and atomic macros are pg_prim.h's; the host side (row_input,
+// row_scan, labels_seen, text_out, names_upload) is declared in pg_internal.h
+// and lives at the top of pg_region.hip.
 #pragma once
 #include "pg_internal.h"
 #include "pg_prim.h"
 
 namespace pg {
 
-typedef unsigned long long ull;
-
-#define RG_BLOCK 256
 #define RG_AGG_MIN 4               // lanes of a wave sharing a label before one lane issues for them
-
-#define RG_LOOP(i, n) \
-  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < (n); i += (uint64_t)gridDim.x * blockDim.x)
-
-#define RG_ADD(p, v) (void)__hip_atomic_fetch_add((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#define RG_MAX(p, v) (void)__hip_atomic_fetch_max((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-#define RG_MIN(p, v) (void)__hip_atomic_fetch_min((p), (v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
-
-#define RG_LAUNCH(kern, grid, ...)                                                       \
-  do {                                                                                   \
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(RG_BLOCK), 0, c.stream, __VA_ARGS__);      \
-    PG_HIP(hipGetLastError());                                                           \
-  } while (0)
 
 struct RgRow {
   long long rec, start, end, strand, label;
 };
-// One tile of RG_BLOCK rows (40 bytes each) and the row before it (the halo:
-// row tile * RG_BLOCK - 1, none for tile 0) through LDS, read as contiguous
-// 8-byte loads.  Every thread then takes its own row r and the row before it
-// p (has_prev: there is one).  Called by every thread of the block (two
-// barriers); returns whether the thread has a row.  lds: 5 * (RG_BLOCK + 1) words.
+// The one definition of "a row is used": it has a label and its record a genome.
+__device__ __forceinline__ bool rs_used(const RgRow& r, const int* __restrict__ rec_group) {
+  return r.label >= 0 && rec_group[r.rec] >= 0;
+}
+// One tile of RG_BLOCK rows (40 bytes each) through LDS, read as contiguous
+// 8-byte loads (a wave: 512 contiguous bytes per load); every thread then
+// takes its own row r.  HALO: the row before the tile (row tile * RG_BLOCK - 1,
+// none for tile 0) comes with it, and every thread also takes the row before
+// its own, p (has_prev: there is one).  Called by every thread of the block
+// (two barriers); returns whether the thread has a row.
+// lds: RG_TILE_WORDS(HALO) words.
+#define RG_TILE_WORDS(HALO) (5 * (RG_BLOCK + ((HALO) ? 1 : 0)))
+template <bool HALO>
 __device__ __forceinline__ bool rg_load_tile(const long long* __restrict__ rows, uint64_t n, uint64_t tile,
                                              long long* lds, RgRow& r, RgRow& p, bool& has_prev) {
   const uint64_t base = tile * RG_BLOCK;                   // first row of the tile
-  const uint32_t halo = base ? 1u : 0u;
+  const uint32_t halo = HALO && base ? 1u : 0u;
   const uint32_t cnt = (uint32_t)(n - base < RG_BLOCK ? n - base : (uint64_t)RG_BLOCK);
   const uint32_t nw = 5 * (cnt + halo);
   const long long* src = rows + 5 * (base - halo);
   __syncthreads();                                         // (the previous tile's readers are done)
-  for (uint32_t w = threadIdx.x; w < nw; w += RG_BLOCK) lds[w] = src[w];
+#pragma unroll
+  for (uint32_t k = 0; k < (HALO ? 6u : 5u); ++k) {        // (the halo's five words are a sixth round)
+    const uint32_t w = k * RG_BLOCK + threadIdx.x;
+    if (w < nw) lds[w] = src[w];
+  }
   __syncthreads();
   const bool have = threadIdx.x < cnt;
   has_prev = have && (threadIdx.x + halo) > 0;
   if (have) {
     const long long* q = lds + 5 * (threadIdx.x + halo);
     r.rec = q[0]; r.start = q[1]; r.end = q[2]; r.strand = q[3]; r.label = q[4];
-    if (has_prev) { p.rec = q[-5]; p.start = q[-4]; p.end = q[-3]; p.strand = q[-2]; p.label = q[-1]; }
+    if (HALO && has_prev) { p.rec = q[-5]; p.start = q[-4]; p.end = q[-3]; p.strand = q[-2]; p.label = q[-1]; }
   }
   return have;
+}
+// the tile without a halo: the thread's own row alone
+__device__ __forceinline__ bool rg_load_tile(const long long* __restrict__ rows, uint64_t n, uint64_t tile,
+                                             long long* lds, RgRow& r) {
+  RgRow p;
+  bool has_prev;
+  return rg_load_tile<false>(rows, n, tile, lds, r, p, has_prev);
 }
 __device__ __forceinline__ ull rg_len(const RgRow& r) {
   return r.end >= r.start ? (ull)r.end - (ull)r.start : (ull)r.start - (ull)r.end;

@@ -10,7 +10,7 @@
 // Tables are dense in the label (L = 1 + the largest used label).
 //
 // Steps, each its own launch on c.stream (no hand-shake inside a kernel):
-//   a. k_rg_scan    per row a flag byte (used, run head); the largest used
+//   a. k_row_scan   per row a flag byte (used, run head); the largest used
 //                   label and record, the used and the skipped rows.  The row
 //                   before a tile's first one is loaded with the tile (one
 //                   halo row), so a run that crosses a tile is not cut.
@@ -41,6 +41,11 @@
 //
 // Every sum is an integer and every atomic commutes: the result depends on
 // the input alone, whatever the schedule.
+//
+// The file begins with the host side of what pg_freq, pg_region_graph and
+// pg_region_seqs share (declared in pg_internal.h; the device side is
+// pg_region.h): row_input, k_row_scan / row_scan, labels_seen, text_out and
+// names_upload.
 #include <cstring>
 
 #include "pg_region.h"
@@ -54,39 +59,168 @@ namespace pg {
 #define RG_LINK 1u                 // flag byte of a sorted pair: its key differs from the pair before
 #define RG_GCHG 2u                 //                             its (key, genome) differs
 
-// ------------------------------------------------------------ a. scan
-// rf[i] = RG_USED | RG_HEAD of row i; out[0] = 1 + the largest used label (0: none), out[1] = used rows,
-// out[2] = skipped rows, out[3] = 1 + the largest record of a used row
-__global__ void __launch_bounds__(RG_BLOCK) k_rg_scan(const long long* __restrict__ rows, uint64_t n,
-                                                      const int* __restrict__ rec_group, uint8_t* __restrict__ rf,
-                                                      ull* __restrict__ out) {
-  __shared__ long long lds[5 * (RG_BLOCK + 1)];
+// ------------------------------------------------------------ the shared front end
+// out[0] = 1 + the largest used label (0: none), out[1] = used rows, out[2] = skipped rows,
+// out[3] = 1 + the largest record of a used row, out[4] = used rows with lo < 0 or hi > rec_len[record]
+// (RECLEN only).  FLAGS: rf[i] = RG_USED | RG_HEAD of row i; the row before a tile's first one is loaded
+// with the tile (one halo row), so a run that crosses a tile is not cut.
+template <bool FLAGS, bool RECLEN>
+__global__ void __launch_bounds__(RG_BLOCK) k_row_scan(const long long* __restrict__ rows, uint64_t n,
+                                                       const int* __restrict__ rec_group, uint8_t* __restrict__ rf,
+                                                       const long long* __restrict__ rec_len, ull* __restrict__ out) {
+  __shared__ long long lds[RG_TILE_WORDS(FLAGS)];
   const uint64_t ntiles = (n + RG_BLOCK - 1) / RG_BLOCK;
-  ull top = 0, used = 0, skipped = 0, toprec = 0;
+  ull top = 0, used = 0, skipped = 0, toprec = 0, bad = 0;
   for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
     RgRow r, p;
     bool hp;
-    if (rg_load_tile(rows, n, t, lds, r, p, hp)) {
-      const bool u = r.label >= 0 && rec_group[r.rec] >= 0;
-      // the row before continues into this one: used, same record and strand
-      const bool cont = u && hp && p.rec == r.rec && p.strand == r.strand && p.label >= 0 && rec_group[p.rec] >= 0;
-      rf[t * RG_BLOCK + threadIdx.x] = (uint8_t)((u ? RG_USED : 0u) | (u && !cont ? RG_HEAD : 0u));
+    if (rg_load_tile<FLAGS>(rows, n, t, lds, r, p, hp)) {
+      const bool u = rs_used(r, rec_group);
+      if (FLAGS) {
+        // the row before continues into this one: used, same record and strand
+        const bool cont = u && hp && p.rec == r.rec && p.strand == r.strand && rs_used(p, rec_group);
+        rf[t * RG_BLOCK + threadIdx.x] = (uint8_t)((u ? RG_USED : 0u) | (u && !cont ? RG_HEAD : 0u));
+      }
       used += u;
       skipped += !u;
-      if (u && (ull)r.label + 1 > top) top = (ull)r.label + 1;
-      if (u && (ull)r.rec + 1 > toprec) toprec = (ull)r.rec + 1;
+      if (u) {
+        if (RECLEN) {
+          const long long lo = r.start < r.end ? r.start : r.end, hi = r.start < r.end ? r.end : r.start;
+          bad += lo < 0 || hi > rec_len[r.rec];
+        }
+        if ((ull)r.label + 1 > top) top = (ull)r.label + 1;
+        if ((ull)r.rec + 1 > toprec) toprec = (ull)r.rec + 1;
+      }
     }
   }
   top = rg_wave_max(top);
   toprec = rg_wave_max(toprec);
   used = rg_wave_sum(used);
   skipped = rg_wave_sum(skipped);
+  if (RECLEN) bad = rg_wave_sum(bad);
+  // the block's waves meet in LDS: the five counters are single words that every wave of the grid would
+  // otherwise queue on, so each takes one atomic per block
+  __shared__ ull tot[5];
+  if (threadIdx.x < 5) tot[threadIdx.x] = 0;
+  __syncthreads();
   if ((threadIdx.x & 63) == 0) {
-    if (top) RG_MAX(out, top);
-    if (used) RG_ADD(out + 1, used);
-    if (skipped) RG_ADD(out + 2, skipped);
-    if (toprec) RG_MAX(out + 3, toprec);
+    atomicMax(&tot[0], top);
+    atomicAdd(&tot[1], used);
+    atomicAdd(&tot[2], skipped);
+    atomicMax(&tot[3], toprec);
+    atomicAdd(&tot[4], bad);
   }
+  __syncthreads();
+  if (threadIdx.x < 5 && tot[threadIdx.x]) {
+    if (threadIdx.x == 0 || threadIdx.x == 3) RG_MAX(out + threadIdx.x, tot[threadIdx.x]);
+    else RG_ADD(out + threadIdx.x, tot[threadIdx.x]);
+  }
+}
+
+RowInput row_input(Ctx& c, const char* what, const int64_t* h_rows5, uint64_t n_rows, const int32_t* rec_group,
+                   uint64_t n_records, uint32_t G, bool records_match_always) {
+  const std::string w = std::string(what) + ": ";
+  const auto records_match = [&] {
+    if (n_records != c.n_records)
+      throw Error(-22, w + std::to_string(n_records) + " records, the context has " + std::to_string(c.n_records));
+  };
+  if (!rec_group) throw Error(-22, w + "rec_group is NULL");
+  if (records_match_always) records_match();
+  if (!h_rows5) {
+    if (!c.rows_ready) throw Error(-22, w + "no row pass (call pg_rows first, or pass rows)");
+    if (!records_match_always) records_match();
+    n_rows = c.n_rows;
+  }
+  for (uint64_t r = 0; r < n_records; ++r)
+    if (rec_group[r] < -1 || (int64_t)rec_group[r] >= (int64_t)G)
+      throw Error(-22, w + "rec_group[" + std::to_string(r) + "] = " + std::to_string(rec_group[r]) +
+                           " is outside [-1, " + std::to_string(G) + ")");
+  if (h_rows5)
+    for (uint64_t i = 0; i < n_rows; ++i)
+      if (h_rows5[5 * i] < 0 || (uint64_t)h_rows5[5 * i] >= n_records)
+        throw Error(-22, w + "row " + std::to_string(i) + " names record " + std::to_string(h_rows5[5 * i]) +
+                             " of " + std::to_string(n_records));
+  if (G == 0 && n_rows) throw Error(-22, w + "n_groups is 0 with rows");
+
+  RowInput in;
+  in.n = n_rows;
+  in.grid_rows = grid_for((n_rows + RG_BLOCK - 1) / RG_BLOCK, 1, 8u * (unsigned)std::max(1, c.n_cu));
+  in.rows = c.rows_buf.as<long long>();
+  if (h_rows5) {
+    in.up.reserve(40 * (n_rows + 1));
+    if (n_rows) PG_HIP(hipMemcpyAsync(in.up.p, h_rows5, 40 * n_rows, hipMemcpyHostToDevice, c.stream));
+    in.rows = in.up.as<long long>();
+  }
+  in.grpmap.reserve(4 * (n_records + 1));
+  if (n_records) PG_HIP(hipMemcpyAsync(in.grpmap.p, rec_group, 4 * n_records, hipMemcpyHostToDevice, c.stream));
+  in.group = in.grpmap.as<int>();
+  return in;
+}
+
+RowScan row_scan(Ctx& c, const char* what, const RowInput& in, uint8_t* rf, const long long* rec_len) {
+  ull h[5] = {0, 0, 0, 0, 0};
+  if (in.n) {
+    DevBuf ctr;
+    ctr.reserve(40);
+    PG_HIP(hipMemsetAsync(ctr.p, 0, 40, c.stream));
+    if (rf) {
+      PG_HIP(hipMemsetAsync(rf + in.n, 0, 1, c.stream));
+      RG_LAUNCH((k_row_scan<true, false>), in.grid_rows, in.rows, in.n, in.group, rf, rec_len, ctr.as<ull>());
+    } else if (rec_len) {
+      RG_LAUNCH((k_row_scan<false, true>), in.grid_rows, in.rows, in.n, in.group, rf, rec_len, ctr.as<ull>());
+    } else {
+      RG_LAUNCH((k_row_scan<false, false>), in.grid_rows, in.rows, in.n, in.group, rf, rec_len, ctr.as<ull>());
+    }
+    PG_HIP(hipMemcpyAsync(h, ctr.p, 40, hipMemcpyDeviceToHost, c.stream));
+    c.sync();
+  }
+  if (h[4]) throw Error(-22, std::string(what) + ": " + std::to_string(h[4]) + " used rows reach outside their record");
+  if (h[0] > (1ull << 31))
+    throw Error(-34, std::string(what) + ": the largest used label is " + std::to_string(h[0] - 1) +
+                         ": the dense tables take labels below 2^31");
+  return RowScan{h[0], h[1], h[2], h[3]};
+}
+
+uint64_t labels_seen(Ctx& c, const uint8_t* flag, uint64_t L, DevBuf& labs) {
+  DevBuf cnt;
+  labs.reserve(8 * (L + 1));
+  return select_flagged(c, rocprim::counting_iterator<long long>(0), flag, labs.as<long long>(), L, cnt);
+}
+
+bool text_wanted(uint64_t total, const char* out, uint64_t cap, int fd, const char* what) {
+  if (!out && fd < 0) return false;
+  if (out && cap < total) throw Error(-34, std::string(what) + ": buffer too small");
+  return true;
+}
+uint64_t text_out(Ctx& c, const void* d_text, uint64_t total, char* out, uint64_t cap, int fd, const char* what,
+                  const char* what_fd) {
+  if (!text_wanted(total, out, cap, fd, what) || !total) return total;
+  if (out) PG_HIP(hipMemcpyAsync(out, d_text, total, hipMemcpyDeviceToHost, c.stream));
+  c.sync();                                                // (text_to_fd reads on streams of its own)
+  if (!out) text_to_fd(c, static_cast<const uint8_t*>(d_text), total, fd, what_fd);
+  return total;
+}
+
+DevNames names_upload(Ctx& c, const char* what, const char* names, const int64_t* name_off, uint64_t n_names,
+                      uint64_t n_needed, const char* noun) {
+  if (!name_off) throw Error(-22, std::string(what) + ": name_off is NULL");
+  if (n_names < n_needed)
+    throw Error(-22, std::string(what) + ": " + std::to_string(n_names) + " names, the " + noun + " need " +
+                         std::to_string(n_needed));
+  for (uint64_t r = 0; r < n_names; ++r)
+    if (name_off[r] < 0 || name_off[r + 1] < name_off[r])
+      throw Error(-22, std::string(what) + ": name_off is not ascending from 0 up");
+  const uint64_t nbytes = (uint64_t)name_off[n_names];
+  if (nbytes && !names) throw Error(-22, std::string(what) + ": names is NULL");
+  DevNames d;
+  d.buf.reserve(8 * (n_names + 1) + nbytes + 16);
+  long long* off = d.buf.as<long long>();
+  char* bytes = reinterpret_cast<char*>(off + n_names + 1);
+  PG_HIP(hipMemcpyAsync(off, name_off, 8 * (n_names + 1), hipMemcpyHostToDevice, c.stream));
+  if (nbytes) PG_HIP(hipMemcpyAsync(bytes, names, nbytes, hipMemcpyHostToDevice, c.stream));
+  d.off = off;
+  d.bytes = bytes;
+  return d;
 }
 
 // ------------------------------------------------------------ b. steps, paths, pairs
@@ -115,12 +249,12 @@ __global__ void __launch_bounds__(RG_BLOCK) k_rg_emit(const long long* __restric
                                                       long long* __restrict__ tail_start,
                                                       long long* __restrict__ tail_end, ull* __restrict__ pkey,
                                                       ull* __restrict__ pgen) {
-  __shared__ long long lds[5 * (RG_BLOCK + 1)];
+  __shared__ long long lds[RG_TILE_WORDS(true)];
   const uint64_t ntiles = (n + RG_BLOCK - 1) / RG_BLOCK;
   for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
     RgRow r, p;
     bool hp;
-    if (!rg_load_tile(rows, n, t, lds, r, p, hp)) continue;
+    if (!rg_load_tile<true>(rows, n, t, lds, r, p, hp)) continue;
     const uint64_t i = t * RG_BLOCK + threadIdx.x;
     const uint32_t f = rf[i];
     if (!(f & RG_USED)) continue;
@@ -205,12 +339,11 @@ __global__ void k_rg_linkfin(RgLinks T, const ull* __restrict__ lpos, const ull*
 // ------------------------------------------------------------ d. nodes
 __global__ void __launch_bounds__(RG_BLOCK) k_rg_accum(const long long* __restrict__ rows, uint64_t n,
                                                        const uint8_t* __restrict__ rf, ull* d_rows, ull* d_max) {
-  __shared__ long long lds[5 * (RG_BLOCK + 1)];
+  __shared__ long long lds[RG_TILE_WORDS(false)];
   const uint64_t ntiles = (n + RG_BLOCK - 1) / RG_BLOCK;
   for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    RgRow r, p;
-    bool hp;
-    const bool have = rg_load_tile(rows, n, t, lds, r, p, hp);
+    RgRow r;
+    const bool have = rg_load_tile(rows, n, t, lds, r);
     const bool todo = have && (rf[t * RG_BLOCK + threadIdx.x] & RG_USED);
     const ull lab = todo ? (ull)r.label : 0ull;
     const ull len = todo ? rg_len(r) : 0ull;
@@ -393,58 +526,22 @@ static uint64_t scan_bit(Ctx& c, const uint8_t* f, uint32_t bit, ull* off, uint6
 
 void region_graph(Ctx& c, const int64_t* h_rows5, uint64_t n_rows, const int32_t* rec_group, uint64_t n_records,
                   uint32_t G, uint64_t* n_nodes, uint64_t* n_links, uint64_t* n_paths, uint64_t* n_skipped) {
-  // ---- arguments (pg_freq's list): everything refused here leaves the previous result in place
-  if (!rec_group) throw Error(-22, "pg_region_graph: rec_group is NULL");
-  if (!h_rows5) {
-    if (!c.rows_ready) throw Error(-22, "pg_region_graph: no row pass (call pg_rows first, or pass rows)");
-    if (n_records != c.n_records)
-      throw Error(-22, "pg_region_graph: " + std::to_string(n_records) + " records, the context has " +
-                           std::to_string(c.n_records));
-    n_rows = c.n_rows;
-  }
-  for (uint64_t r = 0; r < n_records; ++r)
-    if (rec_group[r] < -1 || (int64_t)rec_group[r] >= (int64_t)G)
-      throw Error(-22, "pg_region_graph: rec_group[" + std::to_string(r) + "] = " + std::to_string(rec_group[r]) +
-                           " is outside [-1, " + std::to_string(G) + ")");
-  if (h_rows5)
-    for (uint64_t i = 0; i < n_rows; ++i)
-      if (h_rows5[5 * i] < 0 || (uint64_t)h_rows5[5 * i] >= n_records)
-        throw Error(-22, "pg_region_graph: row " + std::to_string(i) + " names record " +
-                             std::to_string(h_rows5[5 * i]) + " of " + std::to_string(n_records));
-  if (G == 0 && n_rows) throw Error(-22, "pg_region_graph: n_groups is 0 with rows");
-
-  const uint64_t n = n_rows;
-  const unsigned grid_rows = grid_for((n + RG_BLOCK - 1) / RG_BLOCK, 1, 8u * (unsigned)std::max(1, c.n_cu));
-  DevBuf up, grpmap, ctr, rf;
-  const long long* rows = c.rows_buf.as<long long>();
-  if (h_rows5) {
-    up.reserve(40 * (n + 1));
-    if (n) PG_HIP(hipMemcpyAsync(up.p, h_rows5, 40 * n, hipMemcpyHostToDevice, c.stream));
-    rows = up.as<long long>();
-  }
-  grpmap.reserve(4 * (n_records + 1));
-  if (n_records) PG_HIP(hipMemcpyAsync(grpmap.p, rec_group, 4 * n_records, hipMemcpyHostToDevice, c.stream));
-  const int* d_group = grpmap.as<int>();
+  // ---- arguments: everything refused here leaves the previous result in place
+  const RowInput in = row_input(c, "pg_region_graph", h_rows5, n_rows, rec_group, n_records, G, false);
+  const uint64_t n = in.n;
+  const unsigned grid_rows = in.grid_rows;
+  const long long* rows = in.rows;
+  const int* d_group = in.group;
 
   // ---- a. the flags and the dense size, found before anything is allocated or replaced
-  ull h4[4] = {0, 0, 0, 0};
+  DevBuf rf;
   rf.reserve(n + 16);
-  if (n) {
-    ctr.reserve(32);
-    PG_HIP(hipMemsetAsync(ctr.p, 0, 32, c.stream));
-    PG_HIP(hipMemsetAsync(rf.as<uint8_t>() + n, 0, 1, c.stream));
-    RG_LAUNCH(k_rg_scan, grid_rows, rows, n, d_group, rf.as<uint8_t>(), ctr.as<ull>());
-    PG_HIP(hipMemcpyAsync(h4, ctr.p, 32, hipMemcpyDeviceToHost, c.stream));
-    c.sync();
-  }
-  const uint64_t L = h4[0], nu = h4[1];
-  if (L > (1ull << 31))
-    throw Error(-34, "pg_region_graph: the largest used label is " + std::to_string(L - 1) +
-                         ": the dense tables take labels below 2^31");
+  const RowScan sc = row_scan(c, "pg_region_graph", in, rf.as<uint8_t>(), nullptr);
+  const uint64_t L = sc.L, nu = sc.used;
   const int lb = bits_for(L ? L - 1 : 0);                  // a pair key a << lb | b has at most 62 bits
 
   DevBuf uoff, hoff, steps, paths, tails, keyA, keyB, genA, genB, lf, lnum, gsum, lpos, links, dense, seen, labs,
-      cntb, nodes, tlen, toff, text;
+      nodes, tlen, toff, text;
   uint64_t np = 0, npairs = 0, nl = 0, nn = 0;
   steps.reserve(9 * nu + 64);
   long long* step_label = steps.as<long long>();
@@ -505,16 +602,7 @@ void region_graph(Ctx& c, const int64_t* h_rows5, uint64_t n_rows, const int32_t
     if (nl) RG_LAUNCH(k_rg_degree, grid_for(nl, RG_BLOCK, 1024), T, nl, d_out, d_in);
     seen.reserve(L + 16);
     RG_LAUNCH(k_rg_seen, grid_for(L, RG_BLOCK, 8192), d_rows, L, seen.as<uint8_t>());
-    labs.reserve(8 * (L + 1));
-    cntb.reserve(16);
-    with_temp(c, [&](void* tmp, size_t& bytes) {
-      return rocprim::select(tmp, bytes, rocprim::counting_iterator<long long>(0), seen.as<uint8_t>(),
-                             labs.as<long long>(), cntb.as<ull>(), (size_t)L, c.stream);
-    });
-    ull h = 0;
-    PG_HIP(hipMemcpyAsync(&h, cntb.p, 8, hipMemcpyDeviceToHost, c.stream));
-    c.sync();
-    nn = h;
+    nn = labels_seen(c, seen.as<uint8_t>(), L, labs);
     nodes.reserve(RgNodes::bytes(nn));
     RgNodes N(nodes, nn);
     PG_HIP(hipMemcpyAsync(N.label, labs.p, 8 * nn, hipMemcpyDeviceToDevice, c.stream));
@@ -546,76 +634,61 @@ void region_graph(Ctx& c, const int64_t* h_rows5, uint64_t n_rows, const int32_t
   c.rg_np = np;
   c.rg_nu = nu;
   c.rg_total = hdr + body;
-  c.rg_names = h_rows5 ? h4[3] : c.n_records;
+  c.rg_names = h_rows5 ? sc.names : c.n_records;
   c.rg_ready = true;
   if (n_nodes) *n_nodes = nn;
   if (n_links) *n_links = nl;
   if (n_paths) *n_paths = np;
-  if (n_skipped) *n_skipped = h4[2];
-}
-
-static void rg_need(const Ctx& c, const char* what) {
-  if (!c.rg_ready) throw Error(-22, std::string(what) + ": no region graph (call pg_region_graph first)");
-}
-static void rg_get(Ctx& c, void* dst, const void* src, size_t bytes) {
-  if (dst && bytes) PG_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c.stream));
+  if (n_skipped) *n_skipped = sc.skipped;
 }
 
 void region_nodes(Ctx& c, int64_t* label, uint64_t* n_rows, uint64_t* max_len, uint32_t* n_out, uint32_t* n_in,
                   uint64_t cap) {
-  rg_need(c, "pg_region_nodes");
+  need(c.rg_ready, "pg_region_nodes", NEED_GRAPH);
   const uint64_t nn = c.rg_nn;
   if (cap < nn) throw Error(-34, "pg_region_nodes: buffer too small");
   if (!nn) return;
   RgNodes N(c.rg_nodes, nn);
-  rg_get(c, label, N.label, 8 * nn);
-  rg_get(c, n_rows, N.rows, 8 * nn);
-  rg_get(c, max_len, N.maxlen, 8 * nn);
-  rg_get(c, n_out, N.nout, 4 * nn);
-  rg_get(c, n_in, N.nin, 4 * nn);
+  get(c, label, N.label, 8 * nn);
+  get(c, n_rows, N.rows, 8 * nn);
+  get(c, max_len, N.maxlen, 8 * nn);
+  get(c, n_out, N.nout, 4 * nn);
+  get(c, n_in, N.nin, 4 * nn);
   c.sync();
 }
 
 void region_links(Ctx& c, int64_t* from, int64_t* to, uint64_t* count, uint32_t* n_genomes, uint64_t cap) {
-  rg_need(c, "pg_region_links");
+  need(c.rg_ready, "pg_region_links", NEED_GRAPH);
   const uint64_t nl = c.rg_nl;
   if (cap < nl) throw Error(-34, "pg_region_links: buffer too small");
   if (!nl) return;
   RgLinks T(c.rg_links, nl);
-  rg_get(c, from, T.from, 8 * nl);
-  rg_get(c, to, T.to, 8 * nl);
-  rg_get(c, count, T.count, 8 * nl);
-  rg_get(c, n_genomes, T.ngen, 4 * nl);
+  get(c, from, T.from, 8 * nl);
+  get(c, to, T.to, 8 * nl);
+  get(c, count, T.count, 8 * nl);
+  get(c, n_genomes, T.ngen, 4 * nl);
   c.sync();
 }
 
 void region_paths(Ctx& c, int64_t* record, int64_t* strand, int64_t* lo, int64_t* hi, uint64_t* n_steps,
                   uint64_t cap) {
-  rg_need(c, "pg_region_paths");
+  need(c.rg_ready, "pg_region_paths", NEED_GRAPH);
   const uint64_t np = c.rg_np;
   if (cap < np) throw Error(-34, "pg_region_paths: buffer too small");
   if (!np) return;
   RgPaths P(c.rg_paths, np);
-  rg_get(c, record, P.rec, 8 * np);
-  rg_get(c, strand, P.strand, 8 * np);
-  rg_get(c, lo, P.lo, 8 * np);
-  rg_get(c, hi, P.hi, 8 * np);
-  rg_get(c, n_steps, P.steps, 8 * np);
+  get(c, record, P.rec, 8 * np);
+  get(c, strand, P.strand, 8 * np);
+  get(c, lo, P.lo, 8 * np);
+  get(c, hi, P.hi, 8 * np);
+  get(c, n_steps, P.steps, 8 * np);
   c.sync();
 }
 
 // the links text of the last region_graph: its size (out null, fd < 0), copied into out, or written to fd
 uint64_t format_region_links(Ctx& c, char* out, uint64_t cap, int fd) {
-  rg_need(c, fd >= 0 ? "pg_region_links_format_fd" : "pg_region_links_format");
-  if (!out && fd < 0) return c.rg_total;
-  if (out && cap < c.rg_total) throw Error(-34, "pg_region_links_format: buffer too small");
-  if (out) {
-    PG_HIP(hipMemcpyAsync(out, c.rg_text.p, c.rg_total, hipMemcpyDeviceToHost, c.stream));
-    c.sync();
-  } else {
-    text_to_fd(c, c.rg_text.as<uint8_t>(), c.rg_total, fd, "pg_region_links_format_fd");
-  }
-  return c.rg_total;
+  need(c.rg_ready, fd >= 0 ? "pg_region_links_format_fd" : "pg_region_links_format", NEED_GRAPH);
+  return text_out(c, c.rg_text.p, c.rg_total, out, cap, fd, "pg_region_links_format", "pg_region_links_format_fd");
 }
 
 // the GFA text of the last region_graph with this call's record names (names[name_off[r] ..
@@ -625,20 +698,12 @@ uint64_t format_region_gfa(Ctx& c, const char* names, const int64_t* name_off, u
                            uint64_t cap, int fd, bool seq) {
   const char* what = seq ? (fd >= 0 ? "pg_region_gfa_seq_fd" : "pg_region_gfa_seq")
                          : (fd >= 0 ? "pg_region_gfa_fd" : "pg_region_gfa");
-  rg_need(c, what);
+  need(c.rg_ready, what, NEED_GRAPH);
   if (seq) region_seqs_match(c, what);
-  if (!name_off) throw Error(-22, std::string(what) + ": name_off is NULL");
-  if (n_names < c.rg_names)
-    throw Error(-22, std::string(what) + ": " + std::to_string(n_names) + " names, the paths need " +
-                         std::to_string(c.rg_names));
-  for (uint64_t r = 0; r < n_names; ++r)
-    if (name_off[r] < 0 || name_off[r + 1] < name_off[r])
-      throw Error(-22, std::string(what) + ": name_off is not ascending from 0 up");
-  const uint64_t nbytes = (uint64_t)name_off[n_names];
-  if (nbytes && !names) throw Error(-22, std::string(what) + ": names is NULL");
+  const DevNames nm = names_upload(c, what, names, name_off, n_names, c.rg_names, "paths");
   const uint64_t nn = c.rg_nn, nl = c.rg_nl, nu = c.rg_nu, np = c.rg_np, items = nn + nl + nu;
   const size_t hdr = RG_LIT(RG_GFA_HEADER);
-  DevBuf nm, tlen, toff, text, sdst;
+  DevBuf tlen, toff, text, sdst;
   uint64_t body = 0;
   const ull* slen = seq ? region_seqs_len(c) : nullptr;
   RgNodes N(c.rg_nodes, nn);
@@ -646,32 +711,23 @@ uint64_t format_region_gfa(Ctx& c, const char* names, const int64_t* name_off, u
   RgPaths P(c.rg_paths, np);
   const long long* step_label = c.rg_steps.as<long long>();
   const uint8_t* step_flag = reinterpret_cast<const uint8_t*>(step_label + nu);
-  nm.reserve(8 * (n_names + 1) + nbytes + 16);
-  long long* d_off = nm.as<long long>();
-  char* d_names = reinterpret_cast<char*>(d_off + n_names + 1);
   if (items) {
-    PG_HIP(hipMemcpyAsync(d_off, name_off, 8 * (n_names + 1), hipMemcpyHostToDevice, c.stream));
-    if (nbytes) PG_HIP(hipMemcpyAsync(d_names, names, nbytes, hipMemcpyHostToDevice, c.stream));
     tlen.reserve(8 * (items + 1));
     toff.reserve(8 * (items + 1));
-    RG_LAUNCH(k_rg_glen, grid_for(items, RG_BLOCK, 8192), N, nn, T, nl, step_label, step_flag, nu, P, np, d_off,
+    RG_LAUNCH(k_rg_glen, grid_for(items, RG_BLOCK, 8192), N, nn, T, nl, step_label, step_flag, nu, P, np, nm.off,
               slen, tlen.as<ull>());
     body = excl_scan_total(c, tlen.as<ull>(), toff.as<ull>(), items);
   }
   const uint64_t total = hdr + body;
-  if (!out && fd < 0) return total;
-  if (out && cap < total) throw Error(-34, std::string(what) + ": buffer too small");
+  if (!text_wanted(total, out, cap, fd, what)) return total;
   text.reserve(total + 16);
   PG_HIP(hipMemcpyAsync(text.p, RG_GFA_HEADER, hdr, hipMemcpyHostToDevice, c.stream));
   if (seq) sdst.reserve(8 * (nn + 1));
   if (items)
-    RG_LAUNCH(k_rg_gwrite, grid_for(items, RG_BLOCK, 8192), N, nn, T, nl, step_label, step_flag, nu, P, np, d_names,
-              d_off, toff.as<ull>(), slen, sdst.as<ull>(), text.as<char>() + hdr);
+    RG_LAUNCH(k_rg_gwrite, grid_for(items, RG_BLOCK, 8192), N, nn, T, nl, step_label, step_flag, nu, P, np, nm.bytes,
+              nm.off, toff.as<ull>(), slen, sdst.as<ull>(), text.as<char>() + hdr);
   if (seq) region_seqs_copy(c, sdst.as<ull>(), text.as<char>() + hdr);
-  if (out) PG_HIP(hipMemcpyAsync(out, text.p, total, hipMemcpyDeviceToHost, c.stream));
-  c.sync();
-  if (!out) text_to_fd(c, text.as<uint8_t>(), total, fd, what);
-  return total;
+  return text_out(c, text.p, total, out, cap, fd, what, what);
 }
 
 }  // namespace pg

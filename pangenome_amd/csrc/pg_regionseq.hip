@@ -12,7 +12,7 @@
 // it stands if strand == 1 and reverse complemented otherwise.
 //
 // Steps, each its own launch on c.stream (no hand-shake inside a kernel):
-//   a. k_rs_scan    the largest used label and record, the skipped rows and
+//   a. k_row_scan   the largest used label and record, the skipped rows and
 //                   the used rows whose [lo, hi) leaves their record: all
 //                   known before anything is allocated or replaced
 //   b. k_rs_max     per label the largest length (64-bit atomic max), then
@@ -76,58 +76,15 @@ struct RsTab {
   }
 };
 
-__device__ __forceinline__ bool rs_used(const RgRow& r, const int* __restrict__ rec_group) {
-  return r.label >= 0 && rec_group[r.rec] >= 0;
-}
-
-// ------------------------------------------------------------ a. scan
-// out[0] = 1 + the largest used label (0: none), out[1] = used rows, out[2] = skipped rows,
-// out[3] = 1 + the largest record of a used row, out[4] = used rows with lo < 0 or hi > rec_len[record]
-__global__ void __launch_bounds__(RG_BLOCK) k_rs_scan(const long long* __restrict__ rows, uint64_t n,
-                                                      const int* __restrict__ rec_group,
-                                                      const long long* __restrict__ rec_len, ull* __restrict__ out) {
-  __shared__ long long lds[5 * (RG_BLOCK + 1)];
-  const uint64_t ntiles = (n + RG_BLOCK - 1) / RG_BLOCK;
-  ull top = 0, used = 0, skipped = 0, toprec = 0, bad = 0;
-  for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    RgRow r, p;
-    bool hp;
-    if (rg_load_tile(rows, n, t, lds, r, p, hp)) {
-      const bool u = rs_used(r, rec_group);
-      used += u;
-      skipped += !u;
-      if (u) {
-        const long long lo = r.start < r.end ? r.start : r.end, hi = r.start < r.end ? r.end : r.start;
-        bad += lo < 0 || hi > rec_len[r.rec];
-        if ((ull)r.label + 1 > top) top = (ull)r.label + 1;
-        if ((ull)r.rec + 1 > toprec) toprec = (ull)r.rec + 1;
-      }
-    }
-  }
-  top = rg_wave_max(top);
-  toprec = rg_wave_max(toprec);
-  used = rg_wave_sum(used);
-  skipped = rg_wave_sum(skipped);
-  bad = rg_wave_sum(bad);
-  if ((threadIdx.x & 63) == 0) {
-    if (top) RG_MAX(out, top);
-    if (used) RG_ADD(out + 1, used);
-    if (skipped) RG_ADD(out + 2, skipped);
-    if (toprec) RG_MAX(out + 3, toprec);
-    if (bad) RG_ADD(out + 4, bad);
-  }
-}
-
 // ------------------------------------------------------------ b. arg-max
 // d_max[label] = the largest length of its used rows (zeroed before)
 __global__ void __launch_bounds__(RG_BLOCK) k_rs_max(const long long* __restrict__ rows, uint64_t n,
                                                      const int* __restrict__ rec_group, ull* d_max) {
-  __shared__ long long lds[5 * (RG_BLOCK + 1)];
+  __shared__ long long lds[RG_TILE_WORDS(false)];
   const uint64_t ntiles = (n + RG_BLOCK - 1) / RG_BLOCK;
   for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    RgRow r, p;
-    bool hp;
-    const bool todo = rg_load_tile(rows, n, t, lds, r, p, hp) && rs_used(r, rec_group);
+    RgRow r;
+    const bool todo = rg_load_tile(rows, n, t, lds, r) && rs_used(r, rec_group);
     const ull lab = todo ? (ull)r.label : 0ull;
     const ull len = todo ? rg_len(r) : 0ull;
     // every lane of the wave runs the loop (its conditions are ballots)
@@ -142,12 +99,11 @@ __global__ void __launch_bounds__(RG_BLOCK) k_rs_max(const long long* __restrict
 __global__ void __launch_bounds__(RG_BLOCK) k_rs_first(const long long* __restrict__ rows, uint64_t n,
                                                        const int* __restrict__ rec_group,
                                                        const ull* __restrict__ d_max, ull* d_row) {
-  __shared__ long long lds[5 * (RG_BLOCK + 1)];
+  __shared__ long long lds[RG_TILE_WORDS(false)];
   const uint64_t ntiles = (n + RG_BLOCK - 1) / RG_BLOCK;
   for (uint64_t t = blockIdx.x; t < ntiles; t += gridDim.x) {
-    RgRow r, p;
-    bool hp;
-    bool todo = rg_load_tile(rows, n, t, lds, r, p, hp) && rs_used(r, rec_group);
+    RgRow r;
+    bool todo = rg_load_tile(rows, n, t, lds, r) && rs_used(r, rec_group);
     const ull lab = todo ? (ull)r.label : 0ull;
     todo = todo && rg_len(r) == d_max[lab];
     const ull idx = t * RG_BLOCK + threadIdx.x;
@@ -385,57 +341,19 @@ __global__ void k_rs_match(RsTab T, RgNodes N, uint64_t n, ull* __restrict__ mis
 
 void region_seqs(Ctx& c, const int64_t* h_rows5, uint64_t n_rows, const int32_t* rec_group, uint64_t n_records,
                  uint32_t G, uint64_t* n_regions, uint64_t* n_bases, uint64_t* n_skipped) {
-  // ---- arguments (pg_region_graph's list, and a parse): everything refused here leaves the previous result
-  if (!rec_group) throw Error(-22, "pg_region_seqs: rec_group is NULL");
-  if (!c.parsed) throw Error(-22, "pg_region_seqs: no parse (the bases come from the context's parse)");
-  if (n_records != c.n_records)
-    throw Error(-22, "pg_region_seqs: " + std::to_string(n_records) + " records, the context has " +
-                         std::to_string(c.n_records));
-  if (!h_rows5) {
-    if (!c.rows_ready) throw Error(-22, "pg_region_seqs: no row pass (call pg_rows first, or pass rows)");
-    n_rows = c.n_rows;
-  }
-  for (uint64_t r = 0; r < n_records; ++r)
-    if (rec_group[r] < -1 || (int64_t)rec_group[r] >= (int64_t)G)
-      throw Error(-22, "pg_region_seqs: rec_group[" + std::to_string(r) + "] = " + std::to_string(rec_group[r]) +
-                           " is outside [-1, " + std::to_string(G) + ")");
-  if (h_rows5)
-    for (uint64_t i = 0; i < n_rows; ++i)
-      if (h_rows5[5 * i] < 0 || (uint64_t)h_rows5[5 * i] >= n_records)
-        throw Error(-22, "pg_region_seqs: row " + std::to_string(i) + " names record " +
-                             std::to_string(h_rows5[5 * i]) + " of " + std::to_string(n_records));
-  if (G == 0 && n_rows) throw Error(-22, "pg_region_seqs: n_groups is 0 with rows");
-
-  const uint64_t n = n_rows;
-  const unsigned grid_rows = grid_for((n + RG_BLOCK - 1) / RG_BLOCK, 1, 8u * (unsigned)std::max(1, c.n_cu));
-  DevBuf up, grpmap, ctr;
-  const long long* rows = c.rows_buf.as<long long>();
-  if (h_rows5) {
-    up.reserve(40 * (n + 1));
-    if (n) PG_HIP(hipMemcpyAsync(up.p, h_rows5, 40 * n, hipMemcpyHostToDevice, c.stream));
-    rows = up.as<long long>();
-  }
-  grpmap.reserve(4 * (n_records + 1));
-  if (n_records) PG_HIP(hipMemcpyAsync(grpmap.p, rec_group, 4 * n_records, hipMemcpyHostToDevice, c.stream));
-  const int* d_group = grpmap.as<int>();
+  // ---- arguments (and a parse): everything refused here leaves the previous result in place
+  if (rec_group && !c.parsed) throw Error(-22, "pg_region_seqs: no parse (the bases come from the context's parse)");
+  const RowInput in = row_input(c, "pg_region_seqs", h_rows5, n_rows, rec_group, n_records, G, true);
+  const uint64_t n = in.n;
+  const unsigned grid_rows = in.grid_rows;
+  const long long* rows = in.rows;
+  const int* d_group = in.group;
 
   // ---- a. the dense size and the coordinates, checked before anything is allocated or replaced
-  ull h5[5] = {0, 0, 0, 0, 0};
-  if (n) {
-    ctr.reserve(40);
-    PG_HIP(hipMemsetAsync(ctr.p, 0, 40, c.stream));
-    RG_LAUNCH(k_rs_scan, grid_rows, rows, n, d_group, c.rec_len.as<long long>(), ctr.as<ull>());
-    PG_HIP(hipMemcpyAsync(h5, ctr.p, 40, hipMemcpyDeviceToHost, c.stream));
-    c.sync();
-  }
-  const uint64_t L = h5[0];
-  if (h5[4])
-    throw Error(-22, "pg_region_seqs: " + std::to_string(h5[4]) + " used rows reach outside their record");
-  if (L > (1ull << 31))
-    throw Error(-34, "pg_region_seqs: the largest used label is " + std::to_string(L - 1) +
-                         ": the dense tables take labels below 2^31");
+  const RowScan sc = row_scan(c, "pg_region_seqs", in, nullptr, c.rec_len.as<long long>());
+  const uint64_t L = sc.L;
 
-  DevBuf dense, seen, labs, cntb, tab, plen, blob;
+  DevBuf dense, seen, labs, tab, plen, blob;
   uint64_t nr = 0, bases = 0, pad = 0;
   if (L) {
     // ---- b. dense per-label arrays: the largest length, the first row that has it
@@ -448,16 +366,7 @@ void region_seqs(Ctx& c, const int64_t* h_rows5, uint64_t n_rows, const int32_t*
     // ---- c. the labels seen, their rows, the two offsets
     seen.reserve(L + 16);
     RG_LAUNCH(k_rs_seen, grid_for(L, RG_BLOCK, 8192), d_row, L, seen.as<uint8_t>());
-    labs.reserve(8 * (L + 1));
-    cntb.reserve(16);
-    with_temp(c, [&](void* tmp, size_t& bytes) {
-      return rocprim::select(tmp, bytes, rocprim::counting_iterator<long long>(0), seen.as<uint8_t>(),
-                             labs.as<long long>(), cntb.as<ull>(), (size_t)L, c.stream);
-    });
-    ull h = 0;
-    PG_HIP(hipMemcpyAsync(&h, cntb.p, 8, hipMemcpyDeviceToHost, c.stream));
-    c.sync();
-    nr = h;
+    nr = labels_seen(c, seen.as<uint8_t>(), L, labs);
     tab.reserve(RsTab::bytes(nr));
     RsTab T(tab, nr);
     plen.reserve(8 * (nr + 1));
@@ -488,37 +397,30 @@ void region_seqs(Ctx& c, const int64_t* h_rows5, uint64_t n_rows, const int32_t*
   c.rs_n = nr;
   c.rs_bases = bases;
   c.rs_pad = pad;
-  c.rs_names = h_rows5 ? h5[3] : c.n_records;
+  c.rs_names = h_rows5 ? sc.names : c.n_records;
   c.rs_ready = true;
   if (n_regions) *n_regions = nr;
   if (n_bases) *n_bases = bases;
-  if (n_skipped) *n_skipped = h5[2];
-}
-
-static void rs_need(const Ctx& c, const char* what) {
-  if (!c.rs_ready) throw Error(-22, std::string(what) + ": no region sequences (call pg_region_seqs first)");
-}
-static void rs_get(Ctx& c, void* dst, const void* src, size_t bytes) {
-  if (dst && bytes) PG_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, c.stream));
+  if (n_skipped) *n_skipped = sc.skipped;
 }
 
 void region_seqs_table(Ctx& c, int64_t* label, int64_t* row, int64_t* record, int64_t* start, int64_t* end,
                        int64_t* strand, uint64_t* len, uint64_t* gc, uint64_t* amb, uint64_t* offset, uint64_t cap) {
-  rs_need(c, "pg_region_seqs_table");
+  need(c.rs_ready, "pg_region_seqs_table", NEED_SEQS);
   const uint64_t n = c.rs_n;
   if (cap < n) throw Error(-34, "pg_region_seqs_table: buffer too small");
   if (!n) return;
   RsTab T(c.rs_tab, n);
-  rs_get(c, label, T.label, 8 * n);
-  rs_get(c, row, T.row, 8 * n);
-  rs_get(c, record, T.rec, 8 * n);
-  rs_get(c, start, T.start, 8 * n);
-  rs_get(c, end, T.end, 8 * n);
-  rs_get(c, strand, T.strand, 8 * n);
-  rs_get(c, len, T.len, 8 * n);
-  rs_get(c, gc, T.gc, 8 * n);
-  rs_get(c, amb, T.amb, 8 * n);
-  rs_get(c, offset, T.off, 8 * n);
+  get(c, label, T.label, 8 * n);
+  get(c, row, T.row, 8 * n);
+  get(c, record, T.rec, 8 * n);
+  get(c, start, T.start, 8 * n);
+  get(c, end, T.end, 8 * n);
+  get(c, strand, T.strand, 8 * n);
+  get(c, len, T.len, 8 * n);
+  get(c, gc, T.gc, 8 * n);
+  get(c, amb, T.amb, 8 * n);
+  get(c, offset, T.off, 8 * n);
   c.sync();
 }
 
@@ -533,7 +435,7 @@ const ull* region_seqs_len(Ctx& c) { return RsTab(c.rs_tab, c.rs_n).len; }
 
 // the letters of the last region_seqs, the entries one after another: their number (out null), or copied into out
 uint64_t region_seqs_bases(Ctx& c, uint8_t* out, uint64_t cap) {
-  rs_need(c, "pg_region_seqs_bases");
+  need(c.rs_ready, "pg_region_seqs_bases", NEED_SEQS);
   if (!out) return c.rs_bases;
   if (cap < c.rs_bases) throw Error(-34, "pg_region_seqs_bases: buffer too small");
   if (!c.rs_bases) return 0;
@@ -546,8 +448,8 @@ uint64_t region_seqs_bases(Ctx& c, uint8_t* out, uint64_t cap) {
 }
 
 void region_seqs_match(Ctx& c, const char* what) {
-  rs_need(c, what);
-  if (!c.rg_ready) throw Error(-22, std::string(what) + ": no region graph (call pg_region_graph first)");
+  need(c.rs_ready, what, NEED_SEQS);
+  need(c.rg_ready, what, NEED_GRAPH);
   ull bad = c.rs_n != c.rg_nn;
   if (!bad && c.rs_n) {
     DevBuf ctr;
@@ -568,43 +470,25 @@ void region_seqs_match(Ctx& c, const char* what) {
 uint64_t format_region_fasta(Ctx& c, const char* names, const int64_t* name_off, uint64_t n_names, char* out,
                              uint64_t cap, int fd) {
   const char* what = fd >= 0 ? "pg_region_fasta_fd" : "pg_region_fasta";
-  rs_need(c, what);
-  if (!name_off) throw Error(-22, std::string(what) + ": name_off is NULL");
-  if (n_names < c.rs_names)
-    throw Error(-22, std::string(what) + ": " + std::to_string(n_names) + " names, the entries need " +
-                         std::to_string(c.rs_names));
-  for (uint64_t r = 0; r < n_names; ++r)
-    if (name_off[r] < 0 || name_off[r + 1] < name_off[r])
-      throw Error(-22, std::string(what) + ": name_off is not ascending from 0 up");
-  const uint64_t nbytes = (uint64_t)name_off[n_names];
-  if (nbytes && !names) throw Error(-22, std::string(what) + ": names is NULL");
+  need(c.rs_ready, what, NEED_SEQS);
+  const DevNames nm = names_upload(c, what, names, name_off, n_names, c.rs_names, "entries");
   const uint64_t n = c.rs_n;
-  DevBuf nm, tlen, toff, sdst, text;
+  DevBuf tlen, toff, sdst, text;
   uint64_t total = 0;
   RsTab T(c.rs_tab, n);
-  nm.reserve(8 * (n_names + 1) + nbytes + 16);
-  long long* d_off = nm.as<long long>();
-  char* d_names = reinterpret_cast<char*>(d_off + n_names + 1);
   if (n) {
-    PG_HIP(hipMemcpyAsync(d_off, name_off, 8 * (n_names + 1), hipMemcpyHostToDevice, c.stream));
-    if (nbytes) PG_HIP(hipMemcpyAsync(d_names, names, nbytes, hipMemcpyHostToDevice, c.stream));
     tlen.reserve(8 * (n + 1));
     toff.reserve(8 * (n + 1));
-    RG_LAUNCH(k_rs_flen, grid_for(n, RG_BLOCK, 8192), T, n, d_off, tlen.as<ull>());
+    RG_LAUNCH(k_rs_flen, grid_for(n, RG_BLOCK, 8192), T, n, nm.off, tlen.as<ull>());
     total = excl_scan_total(c, tlen.as<ull>(), toff.as<ull>(), n);
   }
-  if (!out && fd < 0) return total;
-  if (out && cap < total) throw Error(-34, std::string(what) + ": buffer too small");
-  if (!total) return 0;
+  if (!text_wanted(total, out, cap, fd, what) || !total) return total;
   text.reserve(total + 16);
   sdst.reserve(8 * (n + 1));
-  RG_LAUNCH(k_rs_fwrite, grid_for(n, RG_BLOCK, 8192), T, n, d_names, d_off, toff.as<ull>(), sdst.as<ull>(),
+  RG_LAUNCH(k_rs_fwrite, grid_for(n, RG_BLOCK, 8192), T, n, nm.bytes, nm.off, toff.as<ull>(), sdst.as<ull>(),
             text.as<char>());
   region_seqs_copy(c, sdst.as<ull>(), text.as<char>());
-  if (out) PG_HIP(hipMemcpyAsync(out, text.p, total, hipMemcpyDeviceToHost, c.stream));
-  c.sync();
-  if (!out) text_to_fd(c, text.as<uint8_t>(), total, fd, what);
-  return total;
+  return text_out(c, text.p, total, out, cap, fd, what, what);
 }
 
 }  // namespace pg

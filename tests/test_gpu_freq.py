@@ -105,6 +105,34 @@ def test_mixed_label_waves(ctx):
     assert len(ref["labels"]) == n and ref["spectrum_labels"][1] == n
 
 
+FORM_TEXT = {}                                           # n -> the text of the form that ran first
+
+
+@pytest.mark.parametrize("form", [0, 1])
+def test_accumulate_forms(ctx, form):
+    """Both accumulate passes (PG_TUNE_FREQ_FORM 0: aggregated in the wave, 1:
+    every lane its own atomics) at the wave and tile edges of the row loader.
+    Every full wave holds a label shared by 40 lanes, one shared by 2, lanes
+    with a label of their own and unused lanes (label -1, or record 7, which
+    has no genome).  5 genomes over 10 records, both strands; the two forms
+    give the same bytes."""
+    from pangenome_amd import _lib
+    rec_group = (np.arange(10) % 5).astype(np.int32)
+    rec_group[7] = -1
+    ctx.tune(_lib.PG_TUNE_FREQ_FORM, form)
+    try:
+        for n in (1, 63, 64, 65, 255, 256, 257, 513):
+            i = np.arange(n)
+            lab = np.where(i % 64 < 40, 0, np.where(i % 64 < 42, 1, i))
+            lab[16::17] = -1
+            rows = make_rows(i * 10 // n, i * 3, i % 29 + 1, np.where(i % 3 == 0, -1, 1), lab)
+            ref, text = check_device(ctx, rows, rec_group, 5)
+            assert ref["n_skipped"] >= n // 17 and (n < 64 or ref["labels"][:2] == [0, 1])
+            assert FORM_TEXT.setdefault(n, text) == text
+    finally:
+        ctx.tune(_lib.PG_TUNE_FREQ_FORM, 0)
+
+
 def test_label_gaps_and_skips(ctx):
     rec_group = np.array([0, 1, -1, 2], np.int32)
     rows = make_rows([0, 1, 3, 0, 1, 2, 3, 2], [0, 5, 9, 100, 7, 7, 50, 1], [10, 3, 0, 27, 40, 40, 6, 8],

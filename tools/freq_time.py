@@ -12,7 +12,7 @@ warm-up per form, then --reps alternating rounds; median and range of each.
 Prints one JSON line; writes nothing.
 
 Per-kernel split: run it under `rocprofv3 --kernel-trace --stats -- python
-tools/freq_time.py --reps 2` and read the k_fr_* rows.
+tools/freq_time.py --reps 2` and read the k_fr_* and k_row_scan rows.
 """
 import argparse
 import hashlib
