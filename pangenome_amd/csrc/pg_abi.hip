@@ -5,6 +5,7 @@
 
 #include "../../include/pangenome.h"
 #include "pg_internal.h"
+#include "pg_text.h"
 
 struct pg_ctx {
   pg::Ctx c;
@@ -93,8 +94,8 @@ void pg_destroy(pg_ctx* x) {
                         &c.recA_key, &c.recA_mw, &c.ctrA, &c.recS_key[0], &c.recS_key[1], &c.recS_mw[0],
                         &c.recS_mw[1], &c.ctrS, &c.snapA, &c.rseg, &c.k5_ctr, &c.tile_sched, &c.tile_desc, &c.k3_queue,
                         &c.k3_hint, &c.part_cnt, &c.tile_cnt, &c.tile_off, &c.occ, &c.edge_tab, &c.pair_tab,
-                        &c.edge_out, &c.edge_exp, &c.lab_tab, &c.lab_list, &c.rows_buf, &c.text_len, &c.text_off,
-                        &c.text_buf, &c.text_names, &c.clu_text, &c.fr_tab, &c.fr_spec, &c.fr_grp, &c.fr_text,
+                        &c.edge_out, &c.edge_exp, &c.lab_tab, &c.lab_list, &c.rows_buf, &c.xyz_off,
+                        &c.text_buf, &c.clu_text, &c.fr_tab, &c.fr_spec, &c.fr_grp, &c.fr_text,
                         &c.cmp_shared, &c.cmp_curve, &c.rg_nodes, &c.rg_links, &c.rg_paths, &c.rg_steps, &c.rg_text,
                         &c.rs_tab, &c.rs_blob, &c.preload,
                         &c.dump_cnt};
@@ -958,28 +959,13 @@ int pg_rows_format_fd(pg_ctx* x, const char* names, const int64_t* name_off, uin
 }
 
 // ---- text of the side file and the region rows (host only, no device work)
-static inline char* put_u64(char* o, uint64_t v) {
-  char t[24];
-  int n = 0;
-  do { t[n++] = (char)('0' + v % 10); v /= 10; } while (v);
-  while (n) *o++ = t[--n];
-  return o;
-}
-static inline char* put_i64(char* o, int64_t v) {
-  if (v < 0) { *o++ = '-'; return put_u64(o, (uint64_t)0 - (uint64_t)v); }
-  return put_u64(o, (uint64_t)v);
-}
-
 uint64_t pg_format_xyz(const uint64_t* t, const int64_t* counts, uint64_t n, char* out, uint64_t cap) {
   if (!out) return n * 106;                               // upper bound: 4 x 20 digits + count + 5 separators
   if (cap < n * 106) return 0;
-  char* o = out;
-  for (uint64_t i = 0; i < n; ++i) {
-    o = put_u64(o, t[4 * i]); *o++ = '_'; o = put_u64(o, t[4 * i + 1]); *o++ = '\t';
-    o = put_u64(o, t[4 * i + 2]); *o++ = '_'; o = put_u64(o, t[4 * i + 3]); *o++ = '\t';
-    o = put_i64(o, counts[i]); *o++ = '\n';
-  }
-  return (uint64_t)(o - out);
+  const pg::XyzLine line{reinterpret_cast<const pg::ull*>(t), reinterpret_cast<const long long*>(counts)};
+  pg::TextWrite s{out, out};
+  for (uint64_t i = 0; i < n; ++i) line(s, i);
+  return (uint64_t)(s.o - out);
 }
 
 uint64_t pg_format_rows(const int64_t* rows5, uint64_t n, const char* names, const int64_t* name_off, char* out,
@@ -991,16 +977,11 @@ uint64_t pg_format_rows(const int64_t* rows5, uint64_t n, const char* names, con
   }
   if (!out) return need;
   if (cap < need) return 0;
-  char* o = out;
-  for (uint64_t i = 0; i < n; ++i) {
-    const int64_t* w = rows5 + 5 * i;
-    const int64_t r = w[0];
-    std::memcpy(o, names + name_off[r], (size_t)(name_off[r + 1] - name_off[r]));
-    o += name_off[r + 1] - name_off[r];
-    *o++ = '\t'; o = put_i64(o, w[1]); *o++ = '\t'; o = put_i64(o, w[2]);
-    *o++ = '\t'; *o++ = w[3] == 1 ? '+' : '-'; *o++ = '\t'; o = put_i64(o, w[4]); *o++ = '\n';
-  }
-  return (uint64_t)(o - out);
+  const pg::RowLine line{reinterpret_cast<const long long*>(rows5), names,
+                         reinterpret_cast<const long long*>(name_off)};
+  pg::TextWrite s{out, out};
+  for (uint64_t i = 0; i < n; ++i) line(s, i);
+  return (uint64_t)(s.o - out);
 }
 
 }  // extern "C"

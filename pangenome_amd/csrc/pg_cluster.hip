@@ -23,7 +23,7 @@
 #include <cstring>
 
 #include "pg_internal.h"
-#include "pg_prim.h"
+#include "pg_text.h"
 
 namespace pg {
 
@@ -127,25 +127,26 @@ __global__ void k_cc_nodeline(const unsigned* __restrict__ comp, const unsigned*
 }
 
 // ------------------------------------------------------------ text and labels
-// token j of the file: node sm[j] as "<key>_<value>" and one separator
-__global__ void k_mcl_len(const unsigned long long* __restrict__ nkey, const unsigned long long* __restrict__ nval,
-                          const unsigned* __restrict__ sm, uint64_t nu, unsigned long long* __restrict__ len) {
-  RG_LOOP(j, nu) len[j] = ndig(nkey[sm[j]]) + ndig(nval[sm[j]]) + 2;
-}
-__global__ void k_mcl_write(const unsigned long long* __restrict__ nkey, const unsigned long long* __restrict__ nval,
-                            const unsigned* __restrict__ sm, const unsigned* __restrict__ sl, uint64_t nu,
-                            const unsigned long long* __restrict__ off, char* __restrict__ out,
-                            long long* __restrict__ lkey, long long* __restrict__ lval, long long* __restrict__ lid) {
-  RG_LOOP(j, nu) {
+// token j of the file: node sm[j] as "<key>_<value>" and one separator (a tab, or the line's end after
+// the last token of line sl[j]); the write pass also puts the token into the label list, in file order
+struct MclLine {
+  const ull *nkey, *nval;
+  const unsigned *sm, *sl;
+  uint64_t nu;
+  long long *lkey, *lval, *lid;
+  template <class S>
+  __device__ __forceinline__ void operator()(S& s, uint64_t j) const {
     const unsigned m = sm[j];
-    char* o = out + off[j];
-    o = put_dec(o, nkey[m]); *o++ = '_'; o = put_dec(o, nval[m]);
-    *o = (j + 1 == nu || sl[j + 1] != sl[j]) ? '\n' : '\t';
-    lkey[j] = (long long)nkey[m];
-    lval[j] = (long long)nval[m];
-    lid[j] = (long long)sl[j];
+    const ull key = nkey[m], val = nval[m];
+    s.dec(key); s.ch('_'); s.dec(val);
+    s.ch((j + 1 == nu || sl[j + 1] != sl[j]) ? '\n' : '\t');
+    if constexpr (S::writes) {
+      lkey[j] = (long long)key;
+      lval[j] = (long long)val;
+      lid[j] = (long long)sl[j];
+    }
   }
-}
+};
 
 // one thread per item of n, up to 8192 blocks
 #define CC_LAUNCH(kern, n, ...) RG_LAUNCH(kern, grid_for((n), RG_BLOCK, 8192), __VA_ARGS__)
@@ -272,16 +273,16 @@ void cluster_cc(Ctx& c, const uint64_t* h_tuples, const int64_t* h_counts, uint6
     CC_LAUNCH(k_cc_nodeline, nu, comp, line_of_root, nu, nl, ni);
     sort_pairs(c, nl, sl, ni, sm, nu, bits_for(nc));
     // ---- f, g. the `.mcl` text (kept on the device) and the label list in file order
-    c.text_len.reserve(8 * (nu + 1));
-    c.text_off.reserve(8 * (nu + 1));
-    c.text_xyz = c.text_rows = false;          // (their offsets are overwritten)
-    CC_LAUNCH(k_mcl_len, nu, nkey, nval, sm, nu, c.text_len.as<unsigned long long>());
-    c.clu_total = excl_scan_total(c, c.text_len.as<unsigned long long>(), c.text_off.as<unsigned long long>(), nu);
-    c.clu_text.reserve(c.clu_total + 16);
     c.lab_list.reserve(24 * (nu + 1));
     long long* L = c.lab_list.as<long long>();
-    CC_LAUNCH(k_mcl_write, nu, nkey, nval, sm, sl, nu, c.text_off.as<unsigned long long>(), c.clu_text.as<char>(), L,
-              L + nu, L + 2 * nu);
+    const MclLine line{nkey, nval, sm, sl, nu, L, L + nu, L + 2 * nu};
+    // The root keys are done with (k_cc_lines, queued above, read them last), so their storage takes the
+    // line offsets: rk holds 16 nu + 16 bytes, the offsets need 8 (nu + 1), and text_measure's reserve
+    // therefore allocates nothing.
+    DevBuf& off = rk;
+    c.clu_total = text_measure(c, line, nu, off);
+    c.clu_text.reserve(c.clu_total + 16);
+    text_write(c, line, nu, off, c.clu_text.as<char>());
     lab_build(c, L, L + nu, L + 2 * nu, nu);
     c.n_labels = nu;
   } else {

@@ -18,7 +18,7 @@
 //   e. k_fr_spectrum          labels and bases by number of genomes
 //   f. k_fr_groups  a second pass over the rows: per genome rows / bases /
 //                   core / unique bases; k_fr_shell the rest
-//   g. k_fr_len, scan, k_fr_write   the text, kept on the device
+//   g. FrLine through pg_text.h     the text, kept on the device
 //
 // Contention (b): at a low weight cut the rdBG is close to one component, so
 // nearly every row carries one label and five atomics per row would all land
@@ -216,30 +216,6 @@ __global__ void k_fr_shell(ull* __restrict__ grp, uint32_t G) {
 
 // ------------------------------------------------------------ g. text
 #define FR_HEADER "#label\tgenomes\trows\tplus\tbp\tmin\tmax\n"
-__global__ void k_fr_len(const long long* __restrict__ labs, const uint32_t* __restrict__ t_ngen,
-                         const ull* __restrict__ t_rows, const ull* __restrict__ t_plus, const ull* __restrict__ t_bp,
-                         const ull* __restrict__ t_min, const ull* __restrict__ t_max, uint64_t nt,
-                         ull* __restrict__ len) {
-  RG_LOOP(i, nt)
-    len[i] = ndig((ull)labs[i]) + ndig(t_ngen[i]) + ndig(t_rows[i]) + ndig(t_plus[i]) + ndig(t_bp[i]) +
-             ndig(t_min[i]) + ndig(t_max[i]) + 7;
-}
-__global__ void k_fr_write(const long long* __restrict__ labs, const uint32_t* __restrict__ t_ngen,
-                           const ull* __restrict__ t_rows, const ull* __restrict__ t_plus,
-                           const ull* __restrict__ t_bp, const ull* __restrict__ t_min, const ull* __restrict__ t_max,
-                           uint64_t nt, const ull* __restrict__ off, char* __restrict__ out) {
-  RG_LOOP(i, nt) {
-    char* o = out + off[i];
-    o = put_dec(o, (ull)labs[i]); *o++ = '\t';
-    o = put_dec(o, t_ngen[i]); *o++ = '\t';
-    o = put_dec(o, t_rows[i]); *o++ = '\t';
-    o = put_dec(o, t_plus[i]); *o++ = '\t';
-    o = put_dec(o, t_bp[i]); *o++ = '\t';
-    o = put_dec(o, t_min[i]); *o++ = '\t';
-    o = put_dec(o, t_max[i]); *o = '\n';
-  }
-}
-
 // the table's columns inside c.fr_tab (nt entries, W presence words each)
 struct FrCols {
   long long* label;
@@ -258,6 +234,21 @@ struct FrCols {
   }
 };
 
+// <label> <genomes> <rows> <plus> <bp> <min> <max>, tab separated
+struct FrLine {
+  FrCols T;
+  template <class S>
+  __device__ __forceinline__ void operator()(S& s, uint64_t i) const {
+    s.dec((ull)T.label[i]); s.ch('\t');
+    s.dec(T.ngen[i]); s.ch('\t');
+    s.dec(T.rows[i]); s.ch('\t');
+    s.dec(T.plus[i]); s.ch('\t');
+    s.dec(T.bp[i]); s.ch('\t');
+    s.dec(T.mn[i]); s.ch('\t');
+    s.dec(T.mx[i]); s.ch('\n');
+  }
+};
+
 void freq(Ctx& c, const int64_t* h_rows5, uint64_t n_rows, const int32_t* rec_group, uint64_t n_records,
           uint32_t G, uint64_t* n_labels, uint64_t* n_used, uint64_t* n_skipped) {
   // ---- arguments: everything refused here leaves the previous result in place
@@ -273,7 +264,7 @@ void freq(Ctx& c, const int64_t* h_rows5, uint64_t n_rows, const int32_t* rec_gr
   const uint64_t L = sc.L;
 
   // ---- b, c. dense per-label arrays: rows, plus, bases, min, max, [W] presence words
-  DevBuf dense, dflag, dngen, labs, tab, spec, grp, tlen, toff, text;
+  DevBuf dense, dflag, dngen, labs, tab, spec, grp, toff, text;
   uint64_t nt = 0;
   spec.reserve(16 * ((size_t)G + 1));
   grp.reserve(40 * (size_t)G + 16);
@@ -316,20 +307,11 @@ void freq(Ctx& c, const int64_t* h_rows5, uint64_t n_rows, const int32_t* rec_gr
   }
   // ---- g. text: the header, then one line per entry
   const size_t hdr = sizeof(FR_HEADER) - 1;
-  uint64_t body = 0;
-  FrCols T(tab, nt, W);
-  if (nt) {
-    tlen.reserve(8 * (nt + 1));
-    toff.reserve(8 * (nt + 1));
-    RG_LAUNCH(k_fr_len, grid_for(nt, RG_BLOCK, 8192), T.label, T.ngen, T.rows, T.plus, T.bp, T.mn, T.mx, nt,
-              tlen.as<ull>());
-    body = excl_scan_total(c, tlen.as<ull>(), toff.as<ull>(), nt);
-  }
+  const FrLine line{FrCols(tab, nt, W)};
+  const uint64_t body = text_measure(c, line, nt, toff);
   text.reserve(hdr + body + 16);
   PG_HIP(hipMemcpyAsync(text.p, FR_HEADER, hdr, hipMemcpyHostToDevice, c.stream));
-  if (nt)
-    RG_LAUNCH(k_fr_write, grid_for(nt, RG_BLOCK, 8192), T.label, T.ngen, T.rows, T.plus, T.bp, T.mn, T.mx, nt,
-              toff.as<ull>(), text.as<char>() + hdr);
+  text_write(c, line, nt, toff, text.as<char>() + hdr);
   c.sync();
   // ---- the new result replaces the previous one
   c.fr_tab.swap(tab);

@@ -285,10 +285,12 @@ struct Ctx {
   DevBuf rows_buf;                // rows of the last row pass: [n][5] int64
   uint64_t n_rows = 0;
   bool rows_ready = false;        // a row pass has run (rows_buf / n_rows are its result)
-  // text of the last edge or row pass (pg_edges_format / pg_rows_format)
-  DevBuf text_len, text_off, text_buf, text_names;
-  uint64_t text_total = 0;
-  bool text_xyz = false, text_rows = false;
+  // the `.xyz` line offsets of the last edge pass and their total, kept from pg_edges_format's size
+  // call for its fill call (xyz_sized; walk_edges clears it); no other text touches them
+  DevBuf xyz_off;
+  uint64_t xyz_total = 0;
+  bool xyz_sized = false;
+  DevBuf text_buf;                // reusable storage of the `.xyz` and the rows text
   // ---- built-in clustering (pg_cluster.hip): the `.mcl` text of the last pg_cluster_cc
   DevBuf clu_text;
   uint64_t clu_total = 0, n_clusters = 0, n_clu_nodes = 0;

@@ -1,7 +1,7 @@
 // pg_prim.h — what every pass after the build shares: the grid-stride loop,
 // the launch on the context's stream and the no-return agent-scope atomics;
-// rocPRIM calls on the context's stream and scratch; the decimal text helpers.
-// (What only the passes over the region rows share is in pg_region.h.)
+// rocPRIM calls on the context's stream and scratch.  (The texts are pg_text.h's;
+// what only the passes over the region rows share is in pg_region.h.)
 #pragma once
 #include <rocprim/rocprim.hpp>
 
@@ -57,7 +57,7 @@ static uint64_t select_flagged(Ctx& c, In in, const uint8_t* flags, T* out, uint
 }
 [[maybe_unused]] static uint64_t excl_scan_total(Ctx& c, const unsigned long long* len, unsigned long long* off,
                                                  uint64_t n) {
-  // off[0..n]: exclusive prefix sums, off[n] = total
+  // off[0..n]: exclusive prefix sums, off[n] = total (off may be len: the scan works in place)
   PG_HIP(hipMemsetAsync(const_cast<unsigned long long*>(len) + n, 0, 8, c.stream));
   with_temp(c, [&](void* tmp, size_t& bytes) {
     return rocprim::exclusive_scan(tmp, bytes, len, off, 0ull, (size_t)n + 1, rocprim::plus<unsigned long long>(),
@@ -80,17 +80,5 @@ __global__ void k_nodes(const unsigned long long* __restrict__ tup, uint64_t nn,
                         unsigned* __restrict__ val, unsigned long long* __restrict__ pos);
 __global__ void k_gather_key(const unsigned long long* __restrict__ src, const unsigned long long* __restrict__ pos,
                              uint64_t n, unsigned long long* __restrict__ dst);
-
-// decimal digits of v (v >= 0)
-__host__ __device__ __forceinline__ uint32_t ndig(unsigned long long v) {
-  uint32_t d = 1;
-  while (v >= 10ull) { v /= 10ull; ++d; }
-  return d;
-}
-__device__ __forceinline__ char* put_dec(char* o, unsigned long long v) {
-  const uint32_t d = ndig(v);
-  for (uint32_t i = d; i-- > 0;) { o[i] = (char)('0' + v % 10ull); v /= 10ull; }
-  return o + d;
-}
 
 }  // namespace pg

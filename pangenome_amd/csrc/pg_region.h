@@ -3,13 +3,13 @@
 // pg_regionseq.hip, the region sequences): the row and the rule for a used one
 // (RgRow, rs_used), a tile of rows through LDS with or without the row before
 // it (rg_load_tile), the wave reductions, the lanes of a wave grouped by label
-// (rg_by_label), the signed decimals and the node table of the graph.  The
+// (rg_by_label) and the node table of the graph.  The
 // loop, launch and atomic macros are pg_prim.h's; the host side (row_input,
 // row_scan, labels_seen, text_out, names_upload) is declared in pg_internal.h
 // and lives at the top of pg_region.hip.
 #pragma once
 #include "pg_internal.h"
-#include "pg_prim.h"
+#include "pg_text.h"
 
 namespace pg {
 
@@ -108,19 +108,6 @@ __device__ __forceinline__ bool rg_by_label(bool todo, ull lab, Agg&& agg) {
     agg(lab0, mine, (ull)__popcll(m), lane == lead);
   }
   return own;
-}
-
-// signed decimals (a host row's start and end may be negative)
-__device__ __forceinline__ uint32_t ndig_s(long long v) { return v < 0 ? 1 + ndig(0ull - (ull)v) : ndig((ull)v); }
-__device__ __forceinline__ char* put_sdec(char* o, long long v) {
-  if (v < 0) { *o++ = '-'; return put_dec(o, 0ull - (ull)v); }
-  return put_dec(o, (ull)v);
-}
-template <size_t N>
-__device__ __forceinline__ char* put_lit(char* o, const char (&s)[N]) {
-#pragma unroll
-  for (size_t i = 0; i + 1 < N; ++i) o[i] = s[i];
-  return o + (N - 1);
 }
 
 // the node table of the region graph (c.rg_nodes, nn entries)

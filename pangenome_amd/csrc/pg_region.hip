@@ -27,11 +27,12 @@
 //                   links leaving and entering it, into dense arrays with
 //                   integer atomics at agent scope; select + k_rg_gather the
 //                   labels seen
-//   e. k_rg_llen / k_rg_lwrite   the links text, kept on the device;
-//      k_rg_glen / k_rg_gwrite   the GFA text, made by every call with its
-//                   own names: one thread per S line, L line and path step
-//                   (a path's header belongs to its first step, its trailer
-//                   to its last: no thread walks a path)
+//   e. LinkLine    the links text, kept on the device;
+//      GfaLine     the GFA text, made by every call with its own names: one
+//                   thread per S line, L line and path step (a path's header
+//                   belongs to its first step, its trailer to its last: no
+//                   thread walks a path).  Both go through pg_text.h, which
+//                   counts and writes a line by one definition.
 //
 // Contention (d): at a low weight cut one label holds every other row (rows
 // A b A c A d ..., see pg_freq.hip) and is an end of most links.  Each wave
@@ -395,28 +396,18 @@ __global__ void k_rg_gather(RgNodes T, uint64_t nn, const ull* __restrict__ d_ro
 // ------------------------------------------------------------ e. text
 #define RG_LINKS_HEADER "#from\tto\tcount\tgenomes\n"
 #define RG_GFA_HEADER "H\tVN:Z:1.0\n"
-#define RG_S1 "S\t"
-#define RG_S2 "\tLN:i:"                // (after the label: a tab, then `*` or the sequence)
-#define RG_L1 "L\t"
-#define RG_L2 "\t+\t"
-#define RG_L3 "\t+\t0M\tRC:i:"
-#define RG_L4 "\tgn:i:"
-#define RG_P1 "P\t"
-#define RG_P2 "\t*\n"
-#define RG_LIT(s) (sizeof(s) - 1)
 
-__global__ void k_rg_llen(RgLinks T, uint64_t nl, ull* __restrict__ len) {
-  RG_LOOP(i, nl) len[i] = ndig((ull)T.from[i]) + ndig((ull)T.to[i]) + ndig(T.count[i]) + ndig(T.ngen[i]) + 4;
-}
-__global__ void k_rg_lwrite(RgLinks T, uint64_t nl, const ull* __restrict__ off, char* __restrict__ out) {
-  RG_LOOP(i, nl) {
-    char* o = out + off[i];
-    o = put_dec(o, (ull)T.from[i]); *o++ = '\t';
-    o = put_dec(o, (ull)T.to[i]); *o++ = '\t';
-    o = put_dec(o, T.count[i]); *o++ = '\t';
-    o = put_dec(o, T.ngen[i]); *o = '\n';
+// <from> <to> <count> <genomes>, tab separated
+struct LinkLine {
+  RgLinks T;
+  template <class S>
+  __device__ __forceinline__ void operator()(S& s, uint64_t i) const {
+    s.dec((ull)T.from[i]); s.ch('\t');
+    s.dec((ull)T.to[i]); s.ch('\t');
+    s.dec(T.count[i]); s.ch('\t');
+    s.dec(T.ngen[i]); s.ch('\n');
   }
-}
+};
 // the path whose first step is s (there is one): the last p with first[p] <= s
 __device__ __forceinline__ uint64_t rg_path_of(const ull* __restrict__ first, uint64_t np, ull s) {
   uint64_t lo = 0, hi = np;                                // first[lo] <= s < first[hi]
@@ -426,87 +417,54 @@ __device__ __forceinline__ uint64_t rg_path_of(const ull* __restrict__ first, ui
   }
   return lo;
 }
-// items: nn S lines, nl L lines, nu path steps.  slen null: an S line carries `*`; otherwise node i's
-// sequence of slen[i] letters, which this pass leaves a gap for (sdst[i]: where it starts in `out`)
-__global__ void k_rg_glen(RgNodes N, uint64_t nn, RgLinks T, uint64_t nl, const long long* __restrict__ step_label,
-                          const uint8_t* __restrict__ step_flag, uint64_t nu, RgPaths P, uint64_t np,
-                          const long long* __restrict__ name_off, const ull* __restrict__ slen,
-                          ull* __restrict__ len) {
-  RG_LOOP(i, nn + nl + nu) {
-    ull v;
+// Item i of the GFA: nn S lines, then nl L lines, then nu path steps (a path's header belongs to its
+// first step, its trailer to its last).  slen null: an S line carries `*`; otherwise node i's sequence
+// of slen[i] letters, which the line leaves a gap for (sdst[i]: where the gap starts in the text)
+struct GfaLine {
+  RgNodes N;
+  uint64_t nn;
+  RgLinks T;
+  uint64_t nl;
+  const long long* step_label;
+  const uint8_t* step_flag;
+  RgPaths P;
+  uint64_t np;
+  const char* names;
+  const long long* name_off;
+  const ull* slen;
+  ull* sdst;
+  template <class S>
+  __device__ __forceinline__ void operator()(S& s, uint64_t i) const {
     if (i < nn) {
-      v = RG_LIT(RG_S1) + ndig((ull)N.label[i]) + 1 + (slen ? slen[i] : 1ull) + RG_LIT(RG_S2) +
-          ndig(N.maxlen[i]) + 1;
-    } else if (i < nn + nl) {
-      const uint64_t l = i - nn;
-      v = RG_LIT(RG_L1) + ndig((ull)T.from[l]) + RG_LIT(RG_L2) + ndig((ull)T.to[l]) + RG_LIT(RG_L3) +
-          ndig(T.count[l]) + RG_LIT(RG_L4) + ndig(T.ngen[l]) + 1;
-    } else {
-      const uint64_t s = i - nn - nl;
-      const uint32_t f = step_flag[s];
-      v = ndig((ull)step_label[s]) + 1 + ((f & RG_LAST) ? RG_LIT(RG_P2) : 1);
-      if (f & RG_FIRST) {
-        const uint64_t p = rg_path_of(P.first, np, s);
-        const long long r = P.rec[p];
-        v += RG_LIT(RG_P1) + (ull)(name_off[r + 1] - name_off[r]) + 1 + ndig_s(P.lo[p]) + 1 + ndig_s(P.hi[p]) + 3;
-      }
-    }
-    len[i] = v;
-  }
-}
-__global__ void k_rg_gwrite(RgNodes N, uint64_t nn, RgLinks T, uint64_t nl, const long long* __restrict__ step_label,
-                            const uint8_t* __restrict__ step_flag, uint64_t nu, RgPaths P, uint64_t np,
-                            const char* __restrict__ names, const long long* __restrict__ name_off,
-                            const ull* __restrict__ off, const ull* __restrict__ slen, ull* __restrict__ sdst,
-                            char* __restrict__ out) {
-  RG_LOOP(i, nn + nl + nu) {
-    char* o = out + off[i];
-    if (i < nn) {
-      o = put_lit(o, RG_S1);
-      o = put_dec(o, (ull)N.label[i]);
-      *o++ = '\t';
+      s.lit("S\t"); s.dec((ull)N.label[i]); s.ch('\t');
       if (slen) {
-        sdst[i] = (ull)(o - out);
-        o += slen[i];
+        const ull at = s.gap(slen[i]);
+        if constexpr (S::writes) sdst[i] = at;
       } else {
-        *o++ = '*';
+        s.ch('*');
       }
-      o = put_lit(o, RG_S2);
-      o = put_dec(o, N.maxlen[i]);
-      *o = '\n';
+      s.lit("\tLN:i:"); s.dec(N.maxlen[i]); s.ch('\n');
     } else if (i < nn + nl) {
       const uint64_t l = i - nn;
-      o = put_lit(o, RG_L1);
-      o = put_dec(o, (ull)T.from[l]);
-      o = put_lit(o, RG_L2);
-      o = put_dec(o, (ull)T.to[l]);
-      o = put_lit(o, RG_L3);
-      o = put_dec(o, T.count[l]);
-      o = put_lit(o, RG_L4);
-      o = put_dec(o, T.ngen[l]);
-      *o = '\n';
+      s.lit("L\t"); s.dec((ull)T.from[l]);
+      s.lit("\t+\t"); s.dec((ull)T.to[l]);
+      s.lit("\t+\t0M\tRC:i:"); s.dec(T.count[l]);
+      s.lit("\tgn:i:"); s.dec(T.ngen[l]); s.ch('\n');
     } else {
-      const uint64_t s = i - nn - nl;
-      const uint32_t f = step_flag[s];
+      const uint64_t st = i - nn - nl;
+      const uint32_t f = step_flag[st];
       if (f & RG_FIRST) {
-        const uint64_t p = rg_path_of(P.first, np, s);
+        const uint64_t p = rg_path_of(P.first, np, st);
         const long long r = P.rec[p];
-        o = put_lit(o, RG_P1);
-        for (long long b = name_off[r]; b < name_off[r + 1]; ++b) *o++ = names[b];
-        *o++ = ':';
-        o = put_sdec(o, P.lo[p]);
-        *o++ = '-';
-        o = put_sdec(o, P.hi[p]);
-        *o++ = ':';
-        *o++ = P.strand[p] == 1 ? '+' : '-';
-        *o++ = '\t';
+        s.lit("P\t"); s.bytes(names + name_off[r], (ull)(name_off[r + 1] - name_off[r]));
+        s.ch(':'); s.sdec(P.lo[p]); s.ch('-'); s.sdec(P.hi[p]);
+        s.ch(':'); s.ch(P.strand[p] == 1 ? '+' : '-'); s.ch('\t');
       }
-      o = put_dec(o, (ull)step_label[s]);
-      *o++ = '+';
-      if (f & RG_LAST) put_lit(o, RG_P2); else *o = ',';
+      s.dec((ull)step_label[st]); s.ch('+');
+      if (f & RG_LAST) s.lit("\t*\n"); else s.ch(',');
     }
   }
-}
+};
 
 // off[0 .. n]: the flag bytes with `bit` set before each position (f[n] must be 0); returns off[n]
 struct RgBit {
@@ -541,7 +499,7 @@ void region_graph(Ctx& c, const int64_t* h_rows5, uint64_t n_rows, const int32_t
   const int lb = bits_for(L ? L - 1 : 0);                  // a pair key a << lb | b has at most 62 bits
 
   DevBuf uoff, hoff, steps, paths, tails, keyA, keyB, genA, genB, lf, lnum, gsum, lpos, links, dense, seen, labs,
-      nodes, tlen, toff, text;
+      nodes, toff, text;
   uint64_t np = 0, npairs = 0, nl = 0, nn = 0;
   steps.reserve(9 * nu + 64);
   long long* step_label = steps.as<long long>();
@@ -611,17 +569,12 @@ void region_graph(Ctx& c, const int64_t* h_rows5, uint64_t n_rows, const int32_t
     nodes.reserve(RgNodes::bytes(0));
   }
   // ---- e. the links text: the header, then one line per link
-  const size_t hdr = RG_LIT(RG_LINKS_HEADER);
-  uint64_t body = 0;
-  if (nl) {
-    tlen.reserve(8 * (nl + 1));
-    toff.reserve(8 * (nl + 1));
-    RG_LAUNCH(k_rg_llen, grid_for(nl, RG_BLOCK, 8192), T, nl, tlen.as<ull>());
-    body = excl_scan_total(c, tlen.as<ull>(), toff.as<ull>(), nl);
-  }
+  const size_t hdr = sizeof(RG_LINKS_HEADER) - 1;
+  const LinkLine line{T};
+  const uint64_t body = text_measure(c, line, nl, toff);
   text.reserve(hdr + body + 16);
   PG_HIP(hipMemcpyAsync(text.p, RG_LINKS_HEADER, hdr, hipMemcpyHostToDevice, c.stream));
-  if (nl) RG_LAUNCH(k_rg_lwrite, grid_for(nl, RG_BLOCK, 8192), T, nl, toff.as<ull>(), text.as<char>() + hdr);
+  text_write(c, line, nl, toff, text.as<char>() + hdr);
   c.sync();
   // ---- the new result replaces the previous one
   c.rg_nodes.swap(nodes);
@@ -702,30 +655,19 @@ uint64_t format_region_gfa(Ctx& c, const char* names, const int64_t* name_off, u
   if (seq) region_seqs_match(c, what);
   const DevNames nm = names_upload(c, what, names, name_off, n_names, c.rg_names, "paths");
   const uint64_t nn = c.rg_nn, nl = c.rg_nl, nu = c.rg_nu, np = c.rg_np, items = nn + nl + nu;
-  const size_t hdr = RG_LIT(RG_GFA_HEADER);
-  DevBuf tlen, toff, text, sdst;
-  uint64_t body = 0;
-  const ull* slen = seq ? region_seqs_len(c) : nullptr;
-  RgNodes N(c.rg_nodes, nn);
-  RgLinks T(c.rg_links, nl);
-  RgPaths P(c.rg_paths, np);
+  const size_t hdr = sizeof(RG_GFA_HEADER) - 1;
+  DevBuf toff, text, sdst;
   const long long* step_label = c.rg_steps.as<long long>();
-  const uint8_t* step_flag = reinterpret_cast<const uint8_t*>(step_label + nu);
-  if (items) {
-    tlen.reserve(8 * (items + 1));
-    toff.reserve(8 * (items + 1));
-    RG_LAUNCH(k_rg_glen, grid_for(items, RG_BLOCK, 8192), N, nn, T, nl, step_label, step_flag, nu, P, np, nm.off,
-              slen, tlen.as<ull>());
-    body = excl_scan_total(c, tlen.as<ull>(), toff.as<ull>(), items);
-  }
-  const uint64_t total = hdr + body;
+  GfaLine line{RgNodes(c.rg_nodes, nn), nn, RgLinks(c.rg_links, nl), nl, step_label,
+               reinterpret_cast<const uint8_t*>(step_label + nu), RgPaths(c.rg_paths, np), np, nm.bytes, nm.off,
+               seq ? region_seqs_len(c) : nullptr, nullptr};
+  const uint64_t total = hdr + text_measure(c, line, items, toff);
   if (!text_wanted(total, out, cap, fd, what)) return total;
   text.reserve(total + 16);
   PG_HIP(hipMemcpyAsync(text.p, RG_GFA_HEADER, hdr, hipMemcpyHostToDevice, c.stream));
   if (seq) sdst.reserve(8 * (nn + 1));
-  if (items)
-    RG_LAUNCH(k_rg_gwrite, grid_for(items, RG_BLOCK, 8192), N, nn, T, nl, step_label, step_flag, nu, P, np, nm.bytes,
-              nm.off, toff.as<ull>(), slen, sdst.as<ull>(), text.as<char>() + hdr);
+  line.sdst = sdst.as<ull>();
+  text_write(c, line, items, toff, text.as<char>() + hdr);
   if (seq) region_seqs_copy(c, sdst.as<ull>(), text.as<char>() + hdr);
   return text_out(c, text.p, total, out, cap, fd, what, what);
 }

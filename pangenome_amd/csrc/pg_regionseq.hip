@@ -40,7 +40,7 @@
 //                   word; a thread keeps them while its chunks stay in one
 //                   entry, and they reach the table through atomics
 //                   aggregated in the wave (rg_by_label) when it leaves it.
-//   e. k_rs_flen / k_rs_fwrite   the FASTA text, one thread per header;
+//   e. FastaLine (pg_text.h)     the FASTA text, one thread per header;
 //      k_rs_copy    the letters, one thread per 16-byte piece of the blob
 //                   (the FASTA and GFA texts and the export without padding)
 //
@@ -300,39 +300,26 @@ __global__ void __launch_bounds__(RG_BLOCK) k_rs_copy(const uint4* __restrict__ 
   }
 }
 
-#define RS_F1 " len="
-// ><label> <name>:<lo>-<hi>:<+|-> len=<len>\n<sequence>\n
-__global__ void k_rs_flen(RsTab T, uint64_t n, const long long* __restrict__ name_off, ull* __restrict__ tlen) {
-  RG_LOOP(i, n) {
-    const long long r = T.rec[i], s = T.start[i], e = T.end[i];
-    tlen[i] = 1 + ndig((ull)T.label[i]) + 1 + (ull)(name_off[r + 1] - name_off[r]) + 1 + ndig_s(s < e ? s : e) + 1 +
-              ndig_s(s < e ? e : s) + 2 + (sizeof(RS_F1) - 1) + ndig(T.len[i]) + 1 + T.len[i] + 1;
+// ><label> <name>:<lo>-<hi>:<+|-> len=<len>\n<sequence>\n; the line leaves a gap for the letters
+// (sdst[i]: where entry i's gap starts in the text)
+struct FastaLine {
+  RsTab T;
+  const char* names;
+  const long long* name_off;
+  ull* sdst;
+  template <class S>
+  __device__ __forceinline__ void operator()(S& s, uint64_t i) const {
+    const long long r = T.rec[i], st = T.start[i], e = T.end[i];
+    s.ch('>'); s.dec((ull)T.label[i]); s.ch(' ');
+    s.bytes(names + name_off[r], (ull)(name_off[r + 1] - name_off[r]));
+    s.ch(':'); s.sdec(st < e ? st : e); s.ch('-'); s.sdec(st < e ? e : st);
+    s.ch(':'); s.ch(T.strand[i] == 1 ? '+' : '-');
+    s.lit(" len="); s.dec(T.len[i]); s.ch('\n');
+    const ull at = s.gap(T.len[i]);
+    if constexpr (S::writes) sdst[i] = at;
+    s.ch('\n');
   }
-}
-// the headers and the line ends; sdst[i]: where entry i's letters go in `out`
-__global__ void k_rs_fwrite(RsTab T, uint64_t n, const char* __restrict__ names,
-                            const long long* __restrict__ name_off, const ull* __restrict__ toff,
-                            ull* __restrict__ sdst, char* __restrict__ out) {
-  RG_LOOP(i, n) {
-    const long long r = T.rec[i], s = T.start[i], e = T.end[i];
-    char* o = out + toff[i];
-    *o++ = '>';
-    o = put_dec(o, (ull)T.label[i]);
-    *o++ = ' ';
-    for (long long b = name_off[r]; b < name_off[r + 1]; ++b) *o++ = names[b];
-    *o++ = ':';
-    o = put_sdec(o, s < e ? s : e);
-    *o++ = '-';
-    o = put_sdec(o, s < e ? e : s);
-    *o++ = ':';
-    *o++ = T.strand[i] == 1 ? '+' : '-';
-    o = put_lit(o, RS_F1);
-    o = put_dec(o, T.len[i]);
-    *o++ = '\n';
-    sdst[i] = (ull)(o - out);
-    o[T.len[i]] = '\n';
-  }
-}
+};
 // mismatch += the entries whose label or length is not the node's
 __global__ void k_rs_match(RsTab T, RgNodes N, uint64_t n, ull* __restrict__ mismatch) {
   RG_LOOP(i, n)
@@ -473,20 +460,14 @@ uint64_t format_region_fasta(Ctx& c, const char* names, const int64_t* name_off,
   need(c.rs_ready, what, NEED_SEQS);
   const DevNames nm = names_upload(c, what, names, name_off, n_names, c.rs_names, "entries");
   const uint64_t n = c.rs_n;
-  DevBuf tlen, toff, sdst, text;
-  uint64_t total = 0;
-  RsTab T(c.rs_tab, n);
-  if (n) {
-    tlen.reserve(8 * (n + 1));
-    toff.reserve(8 * (n + 1));
-    RG_LAUNCH(k_rs_flen, grid_for(n, RG_BLOCK, 8192), T, n, nm.off, tlen.as<ull>());
-    total = excl_scan_total(c, tlen.as<ull>(), toff.as<ull>(), n);
-  }
+  DevBuf toff, sdst, text;
+  FastaLine line{RsTab(c.rs_tab, n), nm.bytes, nm.off, nullptr};
+  const uint64_t total = text_measure(c, line, n, toff);
   if (!text_wanted(total, out, cap, fd, what) || !total) return total;
   text.reserve(total + 16);
   sdst.reserve(8 * (n + 1));
-  RG_LAUNCH(k_rs_fwrite, grid_for(n, RG_BLOCK, 8192), T, n, nm.bytes, nm.off, toff.as<ull>(), sdst.as<ull>(),
-            text.as<char>());
+  line.sdst = sdst.as<ull>();
+  text_write(c, line, n, toff, text.as<char>());
   region_seqs_copy(c, sdst.as<ull>(), text.as<char>());
   return text_out(c, text.p, total, out, cap, fd, what, what);
 }

@@ -15,7 +15,7 @@
 #include <rocprim/rocprim.hpp>
 
 #include "pg_internal.h"
-#include "pg_prim.h"
+#include "pg_text.h"
 
 namespace pg {
 
@@ -477,54 +477,6 @@ __global__ void k_rows(const Hit* __restrict__ hits, const unsigned long long* _
   }
 }
 
-// ------------------------------------------------------------ text
-__device__ __forceinline__ uint32_t ndig_i(long long v) {
-  return v < 0 ? 1 + ndig((unsigned long long)0 - (unsigned long long)v) : ndig((unsigned long long)v);
-}
-__device__ __forceinline__ char* put_dec_i(char* o, long long v) {
-  if (v < 0) { *o++ = '-'; return put_dec(o, (unsigned long long)0 - (unsigned long long)v); }
-  return put_dec(o, (unsigned long long)v);
-}
-
-// `.xyz` lines "%d_%d\t%d_%d\t%d\n" (:1901), keys printed as unsigned
-__global__ void k_xyz_len(const unsigned long long* __restrict__ tup, const long long* __restrict__ cnt, uint64_t n,
-                          unsigned long long* __restrict__ len) {
-  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x)
-    len[i] = ndig(tup[4 * i]) + ndig(tup[4 * i + 1]) + ndig(tup[4 * i + 2]) + ndig(tup[4 * i + 3]) +
-             ndig_i(cnt[i]) + 5;
-}
-__global__ void k_xyz_write(const unsigned long long* __restrict__ tup, const long long* __restrict__ cnt, uint64_t n,
-                            const unsigned long long* __restrict__ off, char* __restrict__ out) {
-  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    char* o = out + off[i];
-    o = put_dec(o, tup[4 * i]); *o++ = '_'; o = put_dec(o, tup[4 * i + 1]); *o++ = '\t';
-    o = put_dec(o, tup[4 * i + 2]); *o++ = '_'; o = put_dec(o, tup[4 * i + 3]); *o++ = '\t';
-    o = put_dec_i(o, cnt[i]); *o = '\n';
-  }
-}
-
-// region rows "%s\t%d\t%d\t%s\t%d\n" (:1947-1949); qid of record r is
-// names[name_off[r] .. name_off[r+1])
-__global__ void k_rowtxt_len(const long long* __restrict__ rows, uint64_t n, const long long* __restrict__ name_off,
-                             unsigned long long* __restrict__ len) {
-  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const long long* w = rows + 5 * i;
-    len[i] = (unsigned long long)(name_off[w[0] + 1] - name_off[w[0]]) + ndig_i(w[1]) + ndig_i(w[2]) +
-             ndig_i(w[4]) + 6;
-  }
-}
-__global__ void k_rowtxt_write(const long long* __restrict__ rows, uint64_t n, const char* __restrict__ names,
-                               const long long* __restrict__ name_off, const unsigned long long* __restrict__ off,
-                               char* __restrict__ out) {
-  for (uint64_t i = blockIdx.x * (uint64_t)blockDim.x + threadIdx.x; i < n; i += (uint64_t)gridDim.x * blockDim.x) {
-    const long long* w = rows + 5 * i;
-    char* o = out + off[i];
-    for (long long b = name_off[w[0]]; b < name_off[w[0] + 1]; ++b) *o++ = names[b];
-    *o++ = '\t'; o = put_dec_i(o, w[1]); *o++ = '\t'; o = put_dec_i(o, w[2]);
-    *o++ = '\t'; *o++ = w[3] == 1 ? '+' : '-'; *o++ = '\t'; o = put_dec_i(o, w[4]); *o = '\n';
-  }
-}
-
 // ------------------------------------------------------------ labels from edges
 // seq2graph :1932-1944: every `.xyz` node (n0_v0, then n1_v1 of each edge, in
 // file order) that the `.mcl` did not label gets the next label, in order of
@@ -694,7 +646,7 @@ uint64_t walk_edges(Ctx& c, const uint8_t* h_rec_flag, int rc1) {
   std::vector<unsigned long long> so, sc;
   const uint64_t m = walk_collect<0>(c, P, a, c.occ, sizeof(Occ), so, sc);
   c.n_edges = 0;
-  c.text_xyz = false;
+  c.xyz_sized = false;
   // Distinct edges join rdBG members: the edge table starts at 4 slots per
   // rdBG key (C3: 1.93 M keys, 2.5 M edges among 1e8 member occurrences) and
   // grows (x4, up to 2 per occurrence) when a probe sequence runs long.  The
@@ -798,34 +750,16 @@ void export_edges(Ctx& c, uint64_t* tuples, int64_t* counts, int64_t* first_walk
 // (out null, fd < 0), copied into out, or written to descriptor fd
 uint64_t format_edges(Ctx& c, char* out, uint64_t cap, int fd) {
   const uint64_t n = c.n_edges;
-  if (!c.text_xyz) {
-    c.text_len.reserve(8 * (n + 1));
-    c.text_off.reserve(8 * (n + 1));
-    const auto* tup = c.edge_exp.as<unsigned long long>();
-    const auto* ecnt = reinterpret_cast<const long long*>(tup + 4 * n);
-    if (n) {
-      hipLaunchKernelGGL(k_xyz_len, dim3(grid_for(n, 256, 8192)), dim3(256), 0, c.stream, tup, ecnt, n,
-                         c.text_len.as<unsigned long long>());
-      PG_HIP(hipGetLastError());
-    }
-    c.text_total = excl_scan_total(c, c.text_len.as<unsigned long long>(), c.text_off.as<unsigned long long>(), n);
-    c.text_xyz = true;
-    c.text_rows = false;
+  const auto* tup = c.edge_exp.as<ull>();
+  const XyzLine line{tup, reinterpret_cast<const long long*>(tup + 4 * n)};
+  if (!c.xyz_sized) {
+    c.xyz_total = text_measure(c, line, n, c.xyz_off);
+    c.xyz_sized = true;
   }
-  if (!out && fd < 0) return c.text_total;
-  if (out && cap < c.text_total) throw Error(-34, "pg_edges_format: buffer too small");
-  if (n) {
-    c.text_buf.reserve(c.text_total + 16);
-    const auto* tup = c.edge_exp.as<unsigned long long>();
-    const auto* ecnt = reinterpret_cast<const long long*>(tup + 4 * n);
-    hipLaunchKernelGGL(k_xyz_write, dim3(grid_for(n, 256, 8192)), dim3(256), 0, c.stream, tup, ecnt, n,
-                       c.text_off.as<unsigned long long>(), c.text_buf.as<char>());
-    PG_HIP(hipGetLastError());
-    if (out) PG_HIP(hipMemcpyAsync(out, c.text_buf.p, c.text_total, hipMemcpyDeviceToHost, c.stream));
-    c.sync();
-    if (!out) text_to_fd(c, c.text_buf.as<uint8_t>(), c.text_total, fd, "pg_edges_format_fd");
-  }
-  return c.text_total;
+  if (!text_wanted(c.xyz_total, out, cap, fd, "pg_edges_format") || !c.xyz_total) return c.xyz_total;
+  c.text_buf.reserve(c.xyz_total + 16);
+  text_write(c, line, n, c.xyz_off, c.text_buf.as<char>());
+  return text_out(c, c.text_buf.p, c.xyz_total, out, cap, fd, "pg_edges_format", "pg_edges_format_fd");
 }
 
 void lab_build(Ctx& c, const long long* d_key, const long long* d_val, const long long* d_id, uint64_t n) {
@@ -971,7 +905,6 @@ uint64_t walk_rows(Ctx& c, const uint8_t* h_rec_flag, int rc1) {
   const uint64_t nseg = so.size();
   c.n_rows = 0;
   c.rows_ready = true;
-  c.text_rows = false;
   if (nseg == 0 || m == 0) return 0;
   // walk bounds (segments are contiguous in walk order)
   DevBuf meta;
@@ -1024,46 +957,20 @@ void export_rows(Ctx& c, int64_t* rows5, uint64_t cap) {
 
 // the region rows' text of the last row pass; names[name_off[r] ..
 // name_off[r+1]) is record r's qid (R + 1 offsets).  Its size (out null,
-// fd < 0), copied into out, or written to descriptor fd.
+// fd < 0), copied into out, or written to descriptor fd.  The qids are this
+// call's names: nothing of an earlier call is reused.
 uint64_t format_rows_text(Ctx& c, const char* names, const int64_t* name_off, uint64_t n_names, char* out,
                           uint64_t cap, int fd) {
+  const char* what = fd >= 0 ? "pg_rows_format_fd" : "pg_rows_format";
+  const DevNames nm = names_upload(c, what, names, name_off, n_names, c.n_records, "rows");
   const uint64_t n = c.n_rows;
-  {
-    // the qids are this call's names: nothing of an earlier call's upload,
-    // line lengths or offsets is reused (one small copy, one kernel and one
-    // scan next to the write)
-    c.text_names.reserve(8 * (n_names + 1) + (uint64_t)std::max<int64_t>(name_off[n_names], 0) + 16);
-    long long* d_off = c.text_names.as<long long>();
-    char* d_names = reinterpret_cast<char*>(d_off + n_names + 1);
-    PG_HIP(hipMemcpyAsync(d_off, name_off, 8 * (n_names + 1), hipMemcpyHostToDevice, c.stream));
-    if (name_off[n_names] > 0)
-      PG_HIP(hipMemcpyAsync(d_names, names, (size_t)name_off[n_names], hipMemcpyHostToDevice, c.stream));
-    c.text_len.reserve(8 * (n + 1));
-    c.text_off.reserve(8 * (n + 1));
-    if (n) {
-      hipLaunchKernelGGL(k_rowtxt_len, dim3(grid_for(n, 256, 8192)), dim3(256), 0, c.stream,
-                         c.rows_buf.as<long long>(), n, d_off, c.text_len.as<unsigned long long>());
-      PG_HIP(hipGetLastError());
-    }
-    c.text_total = excl_scan_total(c, c.text_len.as<unsigned long long>(), c.text_off.as<unsigned long long>(), n);
-    c.text_rows = true;                       // (text_off now holds the rows' offsets, not the .xyz's)
-    c.text_xyz = false;
-  }
-  if (!out && fd < 0) return c.text_total;
-  if (out && cap < c.text_total) throw Error(-34, "pg_rows_format: buffer too small");
-  if (n) {
-    const long long* d_off = c.text_names.as<long long>();
-    const char* d_names = reinterpret_cast<const char*>(d_off + n_names + 1);
-    c.text_buf.reserve(c.text_total + 16);
-    hipLaunchKernelGGL(k_rowtxt_write, dim3(grid_for(n, 256, 8192)), dim3(256), 0, c.stream,
-                       c.rows_buf.as<long long>(), n, d_names, d_off, c.text_off.as<unsigned long long>(),
-                       c.text_buf.as<char>());
-    PG_HIP(hipGetLastError());
-    if (out) PG_HIP(hipMemcpyAsync(out, c.text_buf.p, c.text_total, hipMemcpyDeviceToHost, c.stream));
-    c.sync();
-    if (!out) text_to_fd(c, c.text_buf.as<uint8_t>(), c.text_total, fd, "pg_rows_format_fd");
-  }
-  return c.text_total;
+  const RowLine line{c.rows_buf.as<long long>(), nm.bytes, nm.off};
+  DevBuf off;
+  const uint64_t total = text_measure(c, line, n, off);
+  if (!text_wanted(total, out, cap, fd, "pg_rows_format") || !total) return total;
+  c.text_buf.reserve(total + 16);
+  text_write(c, line, n, off, c.text_buf.as<char>());
+  return text_out(c, c.text_buf.p, total, out, cap, fd, "pg_rows_format", "pg_rows_format_fd");
 }
 
 }  // namespace pg

@@ -7,7 +7,7 @@ bracketed on the host with perf_counter: one warm-up, then the median of
 --reps runs.  Prints one JSON line; writes nothing.
 
 Per-kernel split: run it under `rocprofv3 --kernel-trace --stats -- python
-tools/cluster_time.py --reps 2` and read the k_cc_* / k_mcl_* / rocprim rows.
+tools/cluster_time.py --reps 2` and read the k_cc_* / k_text_*<MclLine> / rocprim rows.
 """
 import argparse
 import json
