@@ -201,7 +201,9 @@ int pg_dbg_merge_check(const pg_ctx* ctx, uint64_t* rows, uint64_t* sum);
  * partitioned and merged again, a rank's stage A records (h = the table
  * hash of the canonical key, the 26-bit mask word) go to their owners, and
  * only the owners run stages B and C.  The owner of a record is the top
- * log2(nparts) bits of h (nparts a power of two, at most 64), so a rank's
+ * log2(nparts) bits of h (nparts a power of two, at most 64 and at most one
+ * owner per coarse bin of k's keys: 8 at k = 1, 32 at k = 2; every routed
+ * call refuses more with PG_EINVAL before anything runs), so a rank's
  * records for one owner are whole stage A regions.
  * pg_route_stage_a: after pg_parse / pg_set_fasta(_device) + pg_parse, stage
  * A of the build pg_build_dbg would run (same arguments), held for routing;

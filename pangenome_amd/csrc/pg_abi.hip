@@ -530,12 +530,20 @@ static int route_lg(int nparts, const char* what) {
     throw pg::Error(PG_EINVAL, std::string(what) + ": nparts must be a power of two in [1, 64]");
   return __builtin_ctz((unsigned)nparts);
 }
+// At most one owner per coarse bin: 2^min(6, kb) of them (8 at k = 1, 32 at
+// k = 2).  From k, not from Ctx.cbits, which only a build sets: on a fresh
+// context that is still 0, and more owners would rotate h by more than its kb
+// bits (TableView::rotk).
+static void route_bins(const pg_ctx* x, int lg, const char* what) {
+  if (lg > std::min(6, pg::key_bits(x->c.k))) throw pg::Error(PG_EINVAL, std::string(what) + ": more owners than coarse bins");
+}
 
 int pg_route_stage_a(pg_ctx* x, const uint8_t* rec_flags, int extra_empty, int rc0, int nparts, uint64_t* counts,
                      int* sentinel) {
   return guard([&] {
     if (!x || !counts) throw pg::Error(PG_EINVAL, "pg_route_stage_a: bad arguments");
     const int lg = route_lg(nparts, "pg_route_stage_a");
+    route_bins(x, lg, "pg_route_stage_a");                   // before the build: nothing runs for a refused count
     PG_HIP(hipSetDevice(x->c.device));
     x->c.route_req = true;
     try {
@@ -554,6 +562,7 @@ int pg_route_scatter(pg_ctx* x, int nparts, void* d_out, uint64_t out_cap, uint6
   return guard([&] {
     if (!x || !sums || (!d_out && out_cap)) throw pg::Error(PG_EINVAL, "pg_route_scatter: bad arguments");
     const int lg = route_lg(nparts, "pg_route_scatter");
+    route_bins(x, lg, "pg_route_scatter");
     PG_HIP(hipSetDevice(x->c.device));
     pg::route_scatter(x->c, lg, d_out, out_cap, sums);
   });
@@ -574,8 +583,8 @@ int pg_route_merge(pg_ctx* x, const void* d_rows, uint64_t n, int nparts, int se
   return guard([&] {
     if (!x || (!d_rows && n)) throw pg::Error(PG_EINVAL, "pg_route_merge: bad arguments");
     const int lg = route_lg(nparts, "pg_route_merge");
+    route_bins(x, lg, "pg_route_merge");
     PG_HIP(hipSetDevice(x->c.device));
-    if (lg > x->c.cbits && x->c.cbits) throw pg::Error(PG_EINVAL, "pg_route_merge: more owners than coarse bins");
     x->c.merge_sum = x->c.merge_rows = 0;
     pg::merge_dbg(x->c, d_rows, n, 0, sentinel, lg);
     if (n_rdbg) *n_rdbg = x->c.n_rdbg;
@@ -590,8 +599,8 @@ int pg_route_merge_segs(pg_ctx* x, const void* const* d_segs, const uint64_t* n,
     for (int s = 0; s < nseg; ++s)
       if (n[s] && !d_segs[s]) throw pg::Error(PG_EINVAL, "pg_route_merge_segs: a non-empty segment has no rows");
     const int lg = route_lg(nparts, "pg_route_merge_segs");
+    route_bins(x, lg, "pg_route_merge_segs");
     PG_HIP(hipSetDevice(x->c.device));
-    if (lg > x->c.cbits && x->c.cbits) throw pg::Error(PG_EINVAL, "pg_route_merge_segs: more owners than coarse bins");
     x->c.merge_sum = x->c.merge_rows = 0;
     pg::merge_dbg_segs(x->c, d_segs, n, nseg, sentinel, lg);
     if (n_rdbg) *n_rdbg = x->c.n_rdbg;

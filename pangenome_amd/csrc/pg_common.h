@@ -113,7 +113,10 @@ struct TableView {
   uint64_t omask;              // overflow slots - 1
   uint64_t rc_pad, rc_inv;     // rc(): 3(5^(27-k)-1)/4 and 5^-(27-k) mod 2^64 (see rc_key27)
 
-  // rotate left by 0 < r < kb within the kb key bits
+  // rotate left by 0 <= r <= kb within the kb key bits (kb <= 63, h < 2^kb).
+  // r == kb (one owner per key bit pattern: 8 owners at k = 1, 32 at k = 2)
+  // and r == 0 (unperm of that) are the identity: one shift leaves kmask or
+  // gives 0, the other is by 0.
   __host__ __device__ __forceinline__ uint64_t rotk(uint64_t h, uint32_t r) const {
     const uint32_t kb = 64u - (uint32_t)__builtin_clzll(kmask);
     return ((h << r) | (h >> (kb - r))) & kmask;

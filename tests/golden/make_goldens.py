@@ -23,6 +23,9 @@ Each fixture directory gets: ``input.fsa``, ``meta.json``, ``rows.tsv`` (the
 5-field region rows, in order), ``rdbg_weight.xyz`` (the edge file),
 ``dbg_keys.npy``/``dbg_masks.npy`` (the dBG, sorted by key) and
 ``rdbg_keys.npy`` (sorted).  Nothing here is imported by the tests.
+
+``make_goldens.py`` regenerates everything; ``make_goldens.py NAME ...``
+only the named fixtures (main()), leaving the others untouched.
 """
 from __future__ import annotations
 
@@ -354,35 +357,82 @@ def components_mcl(xyz_path: str) -> str:
     return "".join("\t".join(c) + "\n" for c in cc[::2])
 
 
-def main():
+# k of the `edge_k<k>` sweep (c=3): every k in 1..27 but those with an `edge`
+# fixture of their own above (5, 11, 27) and 9 and 26, where edge.fsa has a
+# record of k+1 bases (10 and 27) that pure-Python mode cannot run; polya.fsa
+# stands in there.
+EDGE_SWEEP_K = [k for k in range(1, 28) if k not in (5, 9, 11, 26, 27)]
+POLYA_SWEEP_K = [9, 26]
+
+
+def fixture_table(K):
+    """{name: thunk} of every fixture, in generation order (a fixture that
+    shares a graph file with an earlier one checks itself against it; the
+    `.mcl` fixture reads pan8_k27_c3's edge file)."""
     from pangenome_amd import synth
+    inputs = {}
+
+    def inp(name):
+        if name not in inputs:
+            inputs[name] = {
+                "test": lambda: open(os.path.join(REF, "test", "test.fsa"), "rb").read(),
+                "edge": edge_case_fasta,
+                "polya": polya_fasta,
+                "pan8": lambda: synth.pangenome(8, 20000, snp=0.01, indel=0.001, seed=0xBEEF),
+            }[name]()
+        return inputs[name]
+
+    t = {}
+
+    def fx(name, input_name, k, **kw):
+        t[name] = lambda: run_fixture(K, name, input_name, inp(input_name), k, **kw)
+
+    fx("test_k5", "test", 5)
+    fx("test_k5_c3", "test", 5, c=3)
+    fx("test_k27", "test", 27)
+    fx("test_k3_c1", "test", 3, c=1)
+    fx("test_k1", "test", 1)
+    fx("edge_k27", "edge", 27)
+    fx("edge_k27_c3", "edge", 27, c=3)
+    fx("edge_k11", "edge", 11, c=3)
+    fx("edge_k5", "edge", 5)
+    fx("polya_k27", "polya", 27, c=3)
+    for c in (0, 1, 2, 3):
+        fx("pan8_k27_c%d" % c, "pan8", 27, c=c)
+    fx("pan8_k15", "pan8", 15, c=3)
+    fx("pan8_k27_n", "pan8", 27, c=3, n=70000)
+    fx("pan8_k27_chunk", "pan8", 27, c=3, chunk=30000)
+    t["pan8_k27_mcl"] = lambda: run_fixture(
+        K, "pan8_k27_mcl", "pan8", inp("pan8"), 27, c=3,
+        mcl=components_mcl_from(os.path.join(HERE, "pan8_k27_c3", "rdbg_weight.xyz.gz")))
+    t["resume/pan8_k27_r"] = lambda: run_resume_fixture(K, "pan8_k27_r", "pan8", inp("pan8"), 27, 3, "-r", 100000)
+    t["resume/pan8_k27_R"] = lambda: run_resume_fixture(K, "pan8_k27_R", "pan8", inp("pan8"), 27, 3, "-R", 30000)
+    for k in EDGE_SWEEP_K:
+        fx("edge_k%d" % k, "edge", k, c=3)
+    for k in POLYA_SWEEP_K:
+        fx("polya_k%d" % k, "polya", k, c=3)
+    return t
+
+
+def main(names=()):
+    """No names: every fixture from scratch.  Names (`edge_k13 polya_k9
+    resume/pan8_k27_r ...`): only those, the others left as they are (a named
+    fixture's directory is replaced; its input and graph files are rewritten
+    or, where they exist, checked)."""
     K, shim = load_reference()
-    for d in os.listdir(HERE):
-        if os.path.isdir(os.path.join(HERE, d)) and d != "__pycache__":
-            shutil.rmtree(os.path.join(HERE, d))
     try:
-        test_fsa = open(os.path.join(REF, "test", "test.fsa"), "rb").read()
-        run_fixture(K, "test_k5", "test", test_fsa, 5)
-        run_fixture(K, "test_k5_c3", "test", test_fsa, 5, c=3)
-        run_fixture(K, "test_k27", "test", test_fsa, 27)
-        run_fixture(K, "test_k3_c1", "test", test_fsa, 3, c=1)
-        run_fixture(K, "test_k1", "test", test_fsa, 1)
-        edge = edge_case_fasta()
-        run_fixture(K, "edge_k27", "edge", edge, 27)
-        run_fixture(K, "edge_k27_c3", "edge", edge, 27, c=3)
-        run_fixture(K, "edge_k11", "edge", edge, 11, c=3)
-        run_fixture(K, "edge_k5", "edge", edge, 5)
-        run_fixture(K, "polya_k27", "polya", polya_fasta(), 27, c=3)
-        pan = synth.pangenome(8, 20000, snp=0.01, indel=0.001, seed=0xBEEF)
-        for c in (0, 1, 2, 3):
-            run_fixture(K, "pan8_k27_c%d" % c, "pan8", pan, 27, c=c)
-        run_fixture(K, "pan8_k15", "pan8", pan, 15, c=3)
-        run_fixture(K, "pan8_k27_n", "pan8", pan, 27, c=3, n=70000)
-        run_fixture(K, "pan8_k27_chunk", "pan8", pan, 27, c=3, chunk=30000)
-        mcl = components_mcl_from(os.path.join(HERE, "pan8_k27_c3", "rdbg_weight.xyz.gz"))
-        run_fixture(K, "pan8_k27_mcl", "pan8", pan, 27, c=3, mcl=mcl)
-        run_resume_fixture(K, "pan8_k27_r", "pan8", pan, 27, 3, "-r", 100000)
-        run_resume_fixture(K, "pan8_k27_R", "pan8", pan, 27, 3, "-R", 30000)
+        table = fixture_table(K)
+        unknown = [n for n in names if n not in table]
+        if unknown:
+            raise SystemExit("make_goldens.py: no fixture named %s" % ", ".join(unknown))
+        if not names:
+            for d in os.listdir(HERE):
+                if os.path.isdir(os.path.join(HERE, d)) and d != "__pycache__":
+                    shutil.rmtree(os.path.join(HERE, d))
+        for name in names or table:
+            if name.startswith("resume/") and os.path.isdir(os.path.join(HERE, name)):
+                shutil.rmtree(os.path.join(HERE, name))
+            table[name]()
     finally:
         shutil.rmtree(shim, ignore_errors=True)
 
@@ -399,4 +449,4 @@ def components_mcl_from(xyz_gz):
 
 if __name__ == "__main__":
     sys.path.insert(0, REPO)
-    main()
+    main(sys.argv[1:])

@@ -20,8 +20,14 @@ import walk_util as wu
 
 pytestmark = pytest.mark.gpu
 
-KS = (1, 2, 11, 27)
+# the edges of k: the smallest and the largest keys; 13 and 14, where 5^k (pow5(k), pow5(k - 1) in the walks)
+# passes 2^32 and init_keys gets its high part; 6 and 14, where the coverage pass of the build under the walks
+# changes its smear; 11 and 20 in between (tests/test_gpu_ksweep.py has every k)
+KS = (1, 2, 6, 11, 13, 14, 20, 27)
 PATTERNS = ("alternate", "last", "short", "none", "all")
+# every pattern at k = 11 and 27, "alternate" and "all" at the other k
+FLAG_CASES = [(k, p) for p in PATTERNS for k in (11, 27)] + \
+             [(k, p) for p in ("alternate", "all") for k in KS if k not in (11, 27)]
 TABLES = ("const", "three", "distinct", "cross31", "negative", "minus1", "sparse", "absent", "empty")
 
 
@@ -210,8 +216,7 @@ def test_rows_minus_one_everywhere(ctxs, oracle_mod):
 
 
 # -------------------------------------------------------- 2: rows, rec_flags
-@pytest.mark.parametrize("pattern", PATTERNS)
-@pytest.mark.parametrize("k", (11, 27))
+@pytest.mark.parametrize("k,pattern", FLAG_CASES)
 def test_rows_rec_flags(ctxs, oracle_mod, k, pattern):
     inp, ctx = standard(oracle_mod, k), ctxs(k)
     parse(ctx, inp)
@@ -264,8 +269,7 @@ def test_edges_contended_claims(ctxs, oracle_mod, which):
 
 # ------------------------------------------------------- 5: edges, rec_flags
 @pytest.mark.parametrize("which", ("true", "all"))
-@pytest.mark.parametrize("pattern", PATTERNS)
-@pytest.mark.parametrize("k", (11, 27))
+@pytest.mark.parametrize("k,pattern", FLAG_CASES)
 def test_edges_rec_flags(ctxs, oracle_mod, k, pattern, which):
     inp, ctx = standard(oracle_mod, k), ctxs(k)
     stage(ctx, inp, which)

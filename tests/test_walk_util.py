@@ -7,9 +7,11 @@ import walk_util as wu
 from cc_util import xyz_arrays
 from golden_util import Fixture
 
+KS = (1, 2, 6, 11, 13, 14, 20, 27)      # tests/test_gpu_walks.py's
+
 
 def test_standard_input_shape():
-    for k in (1, 2, 11, 27):
+    for k in KS:
         fasta = wu.standard_fasta(k)
         n, hs, hl = wu.record_table(fasta)
         assert n.shape[0] == 20 and len(fasta) < 40_000
@@ -26,7 +28,7 @@ def test_standard_input_shape():
 
 
 @pytest.mark.parametrize("c", [3, 2])
-@pytest.mark.parametrize("k", [1, 2, 11, 27])
+@pytest.mark.parametrize("k", KS)
 def test_dense_table_makes_every_window_a_hit(oracle_mod, k, c):
     """Under one constant label every walk of a record with n > k is one row
     from 0: each window is a hit, the first (idx 0) is never taken (idx >
