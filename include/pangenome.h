@@ -304,6 +304,30 @@ int pg_labels_export(pg_ctx* ctx, int64_t* key, int64_t* value, int64_t* label, 
  * counts, a node value above 2^32 - 1. */
 int pg_cluster_cc(pg_ctx* ctx, const uint64_t* tuples, const int64_t* counts, uint64_t n_edges, int64_t min_weight,
                   uint64_t* n_clusters, uint64_t* n_nodes);
+/* The cluster curve of the `.xyz` graph: what pg_cluster_cc would form at
+ * every weight cut of a list, from one union-find that survives from the
+ * highest threshold down (the components at a threshold are those at the next
+ * higher one plus the unions of the edges whose count lies between the two).
+ * Input: edges, nodes and node ids exactly as pg_cluster_cc (tuples == NULL:
+ * the last pg_edges where it lies on the device); thresholds[n_thr] strictly
+ * ascending, each >= 1, n_thr <= 4096.
+ * Row i, T = thresholds[i]: edges[i] = the edges with count >= T (self-loops
+ * included); clusters[i], largest[i], singletons[i] = the number of components
+ * pg_cluster_cc(min_weight = T) forms (its *n_clusters), the size of the
+ * biggest (0 with no nodes) and how many have exactly one node.  The result
+ * depends on the input alone.  Integer only.
+ * *n_nodes = the nodes, *max_weight = the largest count (0 with no edges).
+ * n_thr == 0 is the query form: these two alone.  Every output pointer may be
+ * NULL; the four arrays take n_thr entries each.
+ * A pure query: the label table, the text of the last pg_cluster_cc and every
+ * other result of the context are neither read nor replaced.
+ * PG_EINVAL (before any device work): NULL ctx, tuples without counts, tuples
+ * == NULL before any pg_edges, a threshold below 1 or not above the one before
+ * it, n_thr > 4096, thresholds == NULL with n_thr > 0, a node value above
+ * 2^32 - 1.  PG_ERANGE: 2^32 nodes or more. */
+int pg_cluster_sweep(pg_ctx* ctx, const uint64_t* tuples, const int64_t* counts, uint64_t n_edges,
+                     const int64_t* thresholds, uint64_t n_thr, uint64_t* n_nodes, int64_t* max_weight,
+                     uint64_t* edges, uint64_t* clusters, uint64_t* largest, uint64_t* singletons);
 /* The `.mcl` text of the last pg_cluster_cc (kept on the device).  out ==
  * NULL: only *n_bytes (the size) is set; otherwise cap >= that size, else
  * PG_ERANGE.  PG_EINVAL before any pg_cluster_cc. */

@@ -98,6 +98,7 @@ SIGNATURES = {
     "pg_labels_from_edges": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, C.c_int64, _U64P]),
     "pg_labels_export": (C.c_int, [_P, _P, _P, _P, C.c_uint64]),
     "pg_cluster_cc": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int64, _U64P, _U64P]),
+    "pg_cluster_sweep": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint64, _U64P, _I64P, _P, _P, _P, _P]),
     "pg_clusters_format": (C.c_int, [_P, _P, C.c_uint64, _U64P]),
     "pg_clusters_format_fd": (C.c_int, [_P, C.c_int, _U64P]),
     "pg_freq": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, C.c_uint32, _U64P, _U64P, _U64P]),
@@ -568,6 +569,39 @@ class Context:
         self.n_labels = nu.value
         self.label_gen = getattr(self, "label_gen", 0) + 1
         return nc.value, nu.value
+
+    def _sweep(self, thresholds, tuples, counts):
+        """pg_cluster_sweep: (n_nodes, max_weight) and the four arrays."""
+        thr = np.ascontiguousarray(thresholds, dtype=np.int64).reshape(-1)
+        t = None if tuples is None else np.ascontiguousarray(tuples, dtype=np.uint64).reshape(-1, 4)
+        cn = None if counts is None else np.ascontiguousarray(counts, dtype=np.int64)
+        if t is not None and cn is not None and cn.shape[0] != t.shape[0]:
+            raise ValueError("cluster_sweep: %d tuples, %d counts" % (t.shape[0], cn.shape[0]))
+        n = 0 if t is None else t.shape[0]
+        if t is not None and not n:                      # (never NULL: an empty array's pointer may be,
+            t = np.zeros((1, 4), np.uint64)              # and NULL tuples would mean the device edges)
+            cn = None if cn is None else np.zeros(1, np.int64)
+        nu, mw = C.c_uint64(), C.c_int64()
+        out = [np.zeros(thr.shape[0], np.uint64) for _ in range(4)]
+        check(self.lib.pg_cluster_sweep(self.h, ptr(t), ptr(cn), n,
+                                        ptr(thr) if thr.shape[0] else None, thr.shape[0], C.byref(nu), C.byref(mw),
+                                        *[ptr(a) for a in out]), "pg_cluster_sweep")
+        return nu.value, mw.value, thr, out
+
+    def cluster_sweep(self, thresholds, tuples=None, counts=None):
+        """The cluster curve (pg_cluster_sweep): for every threshold of the
+        strictly ascending list, what cluster_cc(min_weight=threshold) would
+        form, from one union-find kept from the highest threshold down.
+        tuples None: the last edges() pass on the device.  A query: the label
+        table and the last cluster_cc's text stay.  Returns a dict of arrays:
+        w, edges (count >= w), clusters, largest, singletons."""
+        _, _, thr, (edges, clusters, largest, singles) = self._sweep(thresholds, tuples, counts)
+        return {"w": thr, "edges": edges, "clusters": clusters, "largest": largest, "singletons": singles}
+
+    def cluster_weights(self, tuples=None, counts=None):
+        """(n_nodes, max_weight) of the edges, max_weight the largest count
+        (0 with no edges): pg_cluster_sweep's query form."""
+        return self._sweep(np.zeros(0, np.int64), tuples, counts)[:2]
 
     def clusters_text(self) -> bytes:
         """The `.mcl` text of the last cluster_cc (pg_clusters_format)."""

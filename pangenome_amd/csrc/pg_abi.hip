@@ -710,6 +710,24 @@ int pg_cluster_cc(pg_ctx* x, const uint64_t* tuples, const int64_t* counts, uint
   });
 }
 
+int pg_cluster_sweep(pg_ctx* x, const uint64_t* tuples, const int64_t* counts, uint64_t n_edges,
+                     const int64_t* thresholds, uint64_t n_thr, uint64_t* n_nodes, int64_t* max_weight,
+                     uint64_t* edges, uint64_t* clusters, uint64_t* largest, uint64_t* singletons) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_cluster_sweep: ctx is NULL");
+    if (tuples && !counts) throw pg::Error(PG_EINVAL, "pg_cluster_sweep: tuples without counts");
+    if (!tuples && !x->c.edges_ready) throw pg::Error(PG_EINVAL, "pg_cluster_sweep: no edges (call pg_edges first)");
+    if (n_thr > SW_MAX_LEVELS) throw pg::Error(PG_EINVAL, "pg_cluster_sweep: more than 4096 thresholds");
+    if (n_thr && !thresholds) throw pg::Error(PG_EINVAL, "pg_cluster_sweep: thresholds is NULL");
+    for (uint64_t i = 0; i < n_thr; ++i)
+      if (thresholds[i] < 1 || (i && thresholds[i] <= thresholds[i - 1]))
+        throw pg::Error(PG_EINVAL, "pg_cluster_sweep: thresholds must be at least 1 and strictly ascending");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::cluster_sweep(x->c, tuples, counts, n_edges, thresholds, n_thr, n_nodes, max_weight, edges, clusters, largest,
+                      singletons);
+  });
+}
+
 int pg_clusters_format(pg_ctx* x, char* out, uint64_t cap, uint64_t* n_bytes) {
   return guard([&] {
     if (!x || !n_bytes) throw pg::Error(PG_EINVAL, "pg_clusters_format: bad arguments");

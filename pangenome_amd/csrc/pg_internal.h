@@ -278,6 +278,7 @@ struct Ctx {
   DevBuf edge_out;                // compacted edge slots
   DevBuf edge_exp;                // edges in first-occurrence order: [n][4] tuple, [n] count, [n] first walk
   uint64_t edge_cap = 0, pair_cap = 0, n_edges = 0;
+  bool edges_ready = false;       // an edge pass has run (edge_exp / n_edges are its result)
   DevBuf lab_tab;                 // label table (hash of (key, value) -> label)
   uint64_t lab_cap = 0;
   DevBuf lab_list;                // the labels in order: [n] key, [n] value, [n] label
@@ -453,6 +454,13 @@ uint64_t format_rows_text(Ctx& c, const char* names, const int64_t* name_off, ui
 // text on the device for format_clusters.
 void cluster_cc(Ctx& c, const uint64_t* h_tuples, const int64_t* h_counts, uint64_t n_edges, int64_t min_weight);
 uint64_t format_clusters(Ctx& c, char* out, uint64_t cap, int fd = -1);
+// The cluster curve: row i describes the components cluster_cc would form at min_weight = thr[i] (thr
+// strictly ascending, nt <= SW_MAX_LEVELS, checked by the caller); nt == 0: the node count and the
+// largest count alone.  Every output may be null.  Reads and replaces no result of the context.
+#define SW_MAX_LEVELS 4096
+void cluster_sweep(Ctx& c, const uint64_t* h_tuples, const int64_t* h_counts, uint64_t n_edges, const int64_t* thr,
+                   uint64_t nt, uint64_t* n_nodes, int64_t* max_weight, uint64_t* edges, uint64_t* clusters,
+                   uint64_t* largest, uint64_t* singletons);
 
 // pg_freq.hip
 // The frequency table of rows (h_rows5 NULL: the last row pass) grouped by

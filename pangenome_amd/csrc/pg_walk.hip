@@ -646,6 +646,7 @@ uint64_t walk_edges(Ctx& c, const uint8_t* h_rec_flag, int rc1) {
   std::vector<unsigned long long> so, sc;
   const uint64_t m = walk_collect<0>(c, P, a, c.occ, sizeof(Occ), so, sc);
   c.n_edges = 0;
+  c.edges_ready = false;
   c.xyz_sized = false;
   // Distinct edges join rdBG members: the edge table starts at 4 slots per
   // rdBG key (C3: 1.93 M keys, 2.5 M edges among 1e8 member occurrences) and
@@ -731,6 +732,7 @@ uint64_t walk_edges(Ctx& c, const uint8_t* h_rec_flag, int rc1) {
     }
   }
   c.n_edges = n_out;
+  c.edges_ready = true;
   return n_out;
 }
 

@@ -1115,6 +1115,10 @@ class GpuShard:
         self.ctx.cluster_cc(tuples, counts, int(min_weight))
         return self.ctx.clusters_text()
 
+    def cluster_sweep(self, tuples, counts, thresholds):
+        """the cluster curve of a host edge list (host.cluster_sweep's dict)"""
+        return self.ctx.cluster_sweep(thresholds, tuples, counts)
+
     def rows_text(self, labels, flags, rc1, names):
         self.ctx.set_labels(*labels)
         self.n_rows = self.ctx.rows_count(flags, bool(rc1))
@@ -1346,7 +1350,10 @@ class DistRun:
     def graph(self, Ns, rc1, brkpt="", cluster=True, min_weight=1, groups=None, orders=0):
         """seq2graph (:1853-1951) over the shards.  cluster="cc": without a
         `.mcl`, rank 0 writes one with the built-in clusterer (on its device,
-        or host.cluster_cc for a backend without one) instead of running mcl.
+        or host.cluster_cc for a backend without one) instead of running mcl;
+        min_weight="auto": rank 0 first makes the cluster curve of the merged
+        edges (the backend's cluster_sweep, or host.cluster_sweep), writes the
+        sweep file and cuts at host.sweep_choice's threshold.
         groups (-g): every rank makes the frequency table of its own rows (on
         its device, or host.freq_table over its row text for a backend without
         one) over one global genome numbering; rank 0 merges them and writes
@@ -1387,6 +1394,15 @@ class DistRun:
             from ._lib import format_xyz
             with open(oname, "wb") as f:                       # :1893-1904
                 f.write(format_xyz(tuples, counts))
+            if cluster == "cc" and min_weight == "auto":
+                # -w auto: the cluster curve of the merged edges, its file, and the weight cut it points to
+                thr = host.sweep_thresholds(int(counts.max()) if len(counts) else 0)
+                sweep = self.sh.cluster_sweep if hasattr(self.sh, "cluster_sweep") else host.cluster_sweep
+                table = sweep(tuples, counts, thr)
+                min_weight = host.sweep_choice(table)
+                host.write_sweep_file(self.qry, table, min_weight)
+                if not os.path.isfile("%s.mcl" % oname):      # (an existing `.mcl` is reused whatever made it)
+                    self.say("# -w auto: %d" % min_weight)
             if cluster:
                 if os.path.isfile("%s.mcl" % oname):
                     self.say("# the mcl has been ran")
@@ -1471,7 +1487,7 @@ def entry_point(argv, out=None, shard_factory=None, device=None, dev_index: int 
     group; rank 0 prints.  `shard_factory(k)` makes the rank's backend
     (default: GpuShard on dev_index)."""
     import torch.distributed as dist
-    from .kmer import compare_orders_arg, manual_print, parse_args
+    from .kmer import compare_orders_arg, manual_print, parse_args, weight_arg
     out = out or sys.stdout
     args = parse_args(argv)
     qry, kmer, Ns = args["-i"], int(args["-k"]), host.eval_number(args["-n"])
@@ -1483,7 +1499,7 @@ def entry_point(argv, out=None, shard_factory=None, device=None, dev_index: int 
         if dist.get_rank() == 0:
             manual_print(out)
         raise SystemExit()
-    clu = dict(cluster="cc", min_weight=int(args["-w"])) if args["-a"] == "cc" else {}
+    clu = dict(cluster="cc", min_weight=weight_arg(args)) if args["-a"] == "cc" else {}
     if args["-g"]:
         clu["groups"] = args["-g"]
     if n_orders:

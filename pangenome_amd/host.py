@@ -257,6 +257,20 @@ def mcl_labels(mcl_text: str):
     return mk, mv, mi, flag
 
 
+def _node_ids(t: np.ndarray):
+    """The nodes of the edges t [E, 4], E > 0: the distinct (key, value) pairs
+    numbered by first appearance (n0_v0, then n1_v1 of each edge, in edge
+    order).  Returns the node ids of each edge's ends [E, 2] and the nodes
+    [U, 2]."""
+    nodes = np.ascontiguousarray(t.reshape(-1, 2))           # slot 2e is (n0, v0), slot 2e + 1 is (n1, v1)
+    vv = nodes.view(np.dtype((np.void, 16))).ravel()
+    _, first, inv = np.unique(vv, return_index=True, return_inverse=True)
+    order = np.argsort(first, kind="stable")                 # groups by first appearance
+    rank = np.empty(order.shape[0], np.int64)
+    rank[order] = np.arange(order.shape[0])
+    return rank[inv.ravel()].reshape(-1, 2), nodes[first[order]]
+
+
 def cluster_cc(tuples: np.ndarray, counts: np.ndarray, min_weight: int = 1):
     """The built-in clusterer's specification (pg_cluster_cc computes the same
     on the device): the `.xyz` edges with count < min_weight dropped, the
@@ -274,17 +288,10 @@ def cluster_cc(tuples: np.ndarray, counts: np.ndarray, min_weight: int = 1):
     cnt = np.ascontiguousarray(counts, dtype=np.int64)
     if cnt.shape[0] != t.shape[0]:
         raise ValueError("cluster_cc: %d tuples, %d counts" % (t.shape[0], cnt.shape[0]))
-    nodes = np.ascontiguousarray(t.reshape(-1, 2))           # slot 2e is (n0, v0), slot 2e + 1 is (n1, v1)
-    if nodes.shape[0] == 0:
+    if t.shape[0] == 0:
         z = np.zeros(0, np.int64)
         return "", z, z.copy(), z.copy()
-    vv = nodes.view(np.dtype((np.void, 16))).ravel()
-    _, first, inv = np.unique(vv, return_index=True, return_inverse=True)
-    order = np.argsort(first, kind="stable")                 # groups by first appearance
-    rank = np.empty(order.shape[0], np.int64)
-    rank[order] = np.arange(order.shape[0])
-    ids = rank[inv.ravel()].reshape(-1, 2)                   # node ids of each edge's ends
-    uniq = nodes[first[order]]
+    ids, uniq = _node_ids(t)
     U = uniq.shape[0]
     parent = list(range(U))
     keep = cnt >= int(min_weight)
@@ -312,6 +319,103 @@ def cluster_cc(tuples: np.ndarray, counts: np.ndarray, min_weight: int = 1):
     file_order = np.fromiter((i for _, m in clusters for i in m), dtype=np.int64, count=U)
     line = np.repeat(np.arange(len(clusters), dtype=np.int64), [len(m) for _, m in clusters])
     return text, uniq[file_order, 0].view(np.int64), uniq[file_order, 1].view(np.int64), line
+
+
+SWEEP_MAX_LEVELS = 4096          # pg_cluster_sweep's limit
+
+
+def cluster_sweep(tuples: np.ndarray, counts: np.ndarray, thresholds):
+    """The cluster curve's specification (pg_cluster_sweep computes the same
+    on the device): for every threshold T of the strictly ascending list,
+    the edges with count >= T (self-loops included) and the number of
+    clusters cluster_cc(min_weight=T) forms, the size of the largest (0
+    without nodes) and how many have one node.  One union-find goes from the
+    highest threshold down: the components at T are those at the next higher
+    threshold plus the unions of the edges between the two.  Returns a dict
+    of arrays: w (int64), edges, clusters, largest, singletons (uint64)."""
+    thr = np.ascontiguousarray(thresholds, dtype=np.int64).reshape(-1)
+    if thr.shape[0] > SWEEP_MAX_LEVELS:
+        raise ValueError("cluster_sweep: more than %d thresholds" % SWEEP_MAX_LEVELS)
+    if thr.shape[0] and (thr[0] < 1 or np.any(np.diff(thr) <= 0)):
+        raise ValueError("cluster_sweep: thresholds must be at least 1 and strictly ascending")
+    t = np.ascontiguousarray(tuples, dtype=np.uint64).reshape(-1, 4)
+    cnt = np.ascontiguousarray(counts, dtype=np.int64)
+    if cnt.shape[0] != t.shape[0]:
+        raise ValueError("cluster_sweep: %d tuples, %d counts" % (t.shape[0], cnt.shape[0]))
+    n = thr.shape[0]
+    out = {"w": thr, "edges": np.zeros(n, np.uint64), "clusters": np.zeros(n, np.uint64),
+           "largest": np.zeros(n, np.uint64), "singletons": np.zeros(n, np.uint64)}
+    if t.shape[0] == 0 or n == 0:
+        return out
+    ids, uniq = _node_ids(t)
+    U = uniq.shape[0]
+    level = np.searchsorted(thr, cnt, side="right") - 1      # the last threshold <= count (-1: below them all)
+    parent, size = list(range(U)), [1] * U
+    clusters, largest, singles, kept = U, 1, U, 0
+    for i in range(n - 1, -1, -1):
+        sel = level == i
+        kept += int(sel.sum())
+        for a, b in ids[sel].tolist():
+            while parent[a] != a:                            # find with path halving
+                parent[a] = parent[parent[a]]
+                a = parent[a]
+            while parent[b] != b:
+                parent[b] = parent[parent[b]]
+                b = parent[b]
+            if a != b:                                       # the larger root under the smaller
+                if a < b:
+                    a, b = b, a
+                parent[a] = b
+                singles -= (size[a] == 1) + (size[b] == 1)
+                size[b] += size[a]
+                largest = max(largest, size[b])
+                clusters -= 1
+        out["edges"][i], out["clusters"][i], out["largest"][i], out["singletons"][i] = kept, clusters, largest, singles
+    return out
+
+
+def sweep_thresholds(max_weight: int):
+    """-w auto's thresholds for edges whose largest count is max_weight: every
+    integer 1 .. min(max_weight + 1, 64); past 64 the powers of two 128, 256,
+    ... up to max_weight, then max_weight + 1.  The last is always above every
+    count: the row of single nodes."""
+    top = int(max_weight) + 1
+    thr = list(range(1, min(top, 64) + 1))
+    if top > 64:
+        p = 128
+        while p <= int(max_weight):
+            thr.append(p)
+            p *= 2
+        thr.append(top)
+    return thr
+
+
+def sweep_choice(table) -> int:
+    """-w auto's rule: the threshold whose row has the most clusters of two
+    or more nodes (clusters - singletons); among equals the smallest; 1
+    without rows or when no row has any."""
+    w = np.asarray(table["w"], np.int64)
+    multi = np.asarray(table["clusters"], np.int64) - np.asarray(table["singletons"], np.int64)
+    if w.shape[0] == 0 or multi.max() <= 0:
+        return 1
+    return int(w[int(np.argmax(multi))])                     # (argmax: the first of equals; w ascends)
+
+
+def sweep_text(table, chosen: int) -> str:
+    """`<in>_rdbg_weight.xyz.sweep.tsv`: a header, one line of unsigned
+    decimals per threshold (multi = clusters - singletons), `#auto`."""
+    cols = [np.asarray(table[k]).tolist() for k in ("w", "edges", "clusters", "largest", "singletons")]
+    return ("#w\tedges\tclusters\tlargest\tsingletons\tmulti\n"
+            + "".join("%d\t%d\t%d\t%d\t%d\t%d\n" % (w, e, c, l, s, c - s) for w, e, c, l, s in zip(*cols))
+            + "#auto\t%d\n" % chosen)
+
+
+def write_sweep_file(qry: str, table, chosen: int):
+    """sweep_text as `<qry>_rdbg_weight.xyz.sweep.tsv` (renamed when whole)."""
+    name = qry + "_rdbg_weight.xyz.sweep.tsv"
+    with open(name + ".tmp", "w") as f:
+        f.write(sweep_text(table, chosen))
+    os.replace(name + ".tmp", name)
 
 
 def label_table(mcl_text: str, tuples: np.ndarray):

@@ -264,7 +264,11 @@ def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_
     the files and runs (or reuses) mcl.  cluster="cc": instead of running
     mcl, the built-in clusterer (pg_cluster_cc: edges lighter than min_weight
     dropped, connected components of the rest) writes the `.mcl`; an existing
-    `.mcl` is reused either way.  groups (-g; "record" or a `seqid<TAB>genome`
+    `.mcl` is reused either way.  min_weight="auto" (with cluster="cc"): the
+    cluster curve of the `.xyz` over host.sweep_thresholds is made first
+    (pg_cluster_sweep, on the device edges where they lie), written as
+    `<qry>_rdbg_weight.xyz.sweep.tsv`, and host.sweep_choice's threshold is
+    the weight cut.  groups (-g; "record" or a `seqid<TAB>genome`
     file): after the rows are written, their frequency table is made where
     they lie on the device (pg_freq) and the four `<qry>_fr_*` files written;
     nothing more is printed.  orders (-p, with groups): the genomes are then
@@ -285,6 +289,16 @@ def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_
             g.ctx.edges_write(f.fileno())             # formatted on the device, streamed into the file
         else:
             f.write(format_xyz(*res))
+    if cluster == "cc" and min_weight == "auto":
+        # -w auto: the cluster curve of the `.xyz` just written, its file, and the weight cut it points to
+        if res is None:
+            table = g.ctx.cluster_sweep(host.sweep_thresholds(g.ctx.cluster_weights()[1]))
+        else:
+            table = g.ctx.cluster_sweep(host.sweep_thresholds(int(res[1].max()) if len(res[1]) else 0), *res)
+        min_weight = host.sweep_choice(table)
+        host.write_sweep_file(qry, table, min_weight)
+        if not os.path.isfile("%s.mcl" % oname):      # (an existing `.mcl` is reused whatever made it)
+            print("# -w auto: %d" % min_weight, file=out)
     clustered = False
     if cluster:
         if os.path.isfile("%s.mcl" % oname):
@@ -442,7 +456,8 @@ def manual_print(out=None):
                  "      <in>_fr_links.tsv, _fr_nodes.tsv, _fr_graph.gfa (GFA 1, the genomes as paths), _fr_graph.npz",
                  "  -c: complementary reverse sequence. 00,01,10,11",
                  "  -a: clustering of the rdBG. mcl (run or reuse mcl) or cc (built-in connected components)",
-                 "  -w: with -a cc, drop edges lighter than this weight. default 1"):
+                 "  -w: with -a cc, drop edges lighter than this weight. default 1. auto: the weight with the most clusters of "
+                 "2+ nodes, from the cluster curve written to <in>_rdbg_weight.xyz.sweep.tsv"):
         print(line, file=out)
 
 
@@ -458,6 +473,12 @@ def parse_args(argv):
         elif k[:2] in args and len(k) > 2:
             args[k[:2]] = k[2:]
     return args
+
+
+def weight_arg(args):
+    """-w's value with -a cc: "auto" or an integer (anything else raises
+    ValueError, as int() does)."""
+    return "auto" if args["-w"] == "auto" else int(args["-w"])
 
 
 def compare_orders_arg(args):
@@ -495,7 +516,7 @@ def entry_point(argv, out=None, device=0):
     if not qry or args["-a"] not in ("mcl", "cc") or n_orders is None or links is None or seqs is None:
         manual_print(out)
         raise SystemExit()
-    clu = dict(cluster="cc", min_weight=int(args["-w"])) if args["-a"] == "cc" else {}
+    clu = dict(cluster="cc", min_weight=weight_arg(args)) if args["-a"] == "cc" else {}
     grp = args["-g"]
     if grp:
         clu["groups"] = grp
