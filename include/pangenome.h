@@ -130,7 +130,7 @@ int pg_build_dbg(pg_ctx* ctx, const uint8_t* rec_flags, int extra_empty, int rc0
 
 /* K5: dbg2rdbg (kmer_numba.py:1313-1321 -> build_rdbg_jit_ :1292-1309).
  * The degree scan runs inside pg_build_dbg (every key's masks are final when
- * its table partition is merged; the rdBG keys are materialised there), so
+ * its table partition is merged; the rdBG members are counted there), so
  * this only reports it. */
 int pg_build_rdbg(pg_ctx* ctx, uint64_t* n_rdbg, pg_stats* stats);
 
@@ -141,7 +141,13 @@ int pg_build(pg_ctx* ctx, const uint8_t* rec_flags, int extra_empty, int rc0, ui
 /* dump()'s keys/values (kmer_numba.py:243-261) of the dBG, sorted by key
  * (on the device).  keys == NULL: only *n is set. */
 int pg_dbg_export(pg_ctx* ctx, uint64_t* keys, uint16_t* masks, uint64_t cap, uint64_t* n);
-/* rdBG keys, sorted. keys == NULL: only *n is set. */
+/* rdBG keys, sorted. keys == NULL: only *n is set (the build's count: no
+ * device work).  With keys, the call reads the whole table once (16 bytes per
+ * bucket plus the overflow slots: 0.5 GB for a 2^25-bucket table, whatever the
+ * number of keys), sorts the member keys on the device and copies them back;
+ * it fails with PG_EDEVICE if the table does not hold exactly the members
+ * the build counted.  After a build in the eager form (PG_TUNE_RDBG_KEYS 1)
+ * it gathers the keys that build wrote instead of reading the table. */
 int pg_rdbg_export(pg_ctx* ctx, uint64_t* keys, uint64_t cap, uint64_t* n);
 
 /* ---- npz persistence: dump() / load_on_disk() (kmer_numba.py:243-335).
@@ -713,6 +719,16 @@ uint64_t pg_format_rows(const int64_t* rows5, uint64_t n, const char* names, con
  * to global atomics above; 1 = the global form at every size (the same
  * results; for comparison). */
 #define PG_TUNE_CMP_FORM 23
+/* PG_TUNE_RDBG_KEYS: where the rdBG keys come from.  0 (default) = the
+ * build's range pass only counts the rdBG members, and pg_rdbg_export sweeps
+ * the table for their keys when asked; 1 = the eager form: the range pass
+ * also writes every member's key (about a fifth of its time on a 100-genome
+ * batch, and 8 bytes per key of device memory), and pg_rdbg_export gathers
+ * them without reading the table.  For a caller that exports after every
+ * build of a table too large to sweep each time (the streamed merge's 2^30
+ * bucket tables).  It takes effect at the next build; pg_rdbg_export follows
+ * the form of the last build.  The same keys either way. */
+#define PG_TUNE_RDBG_KEYS 24
 int pg_tune(pg_ctx* ctx, int what, int64_t value);
 
 /* Device bytes the library's buffers hold in this process now (peak == 0)

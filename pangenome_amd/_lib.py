@@ -38,6 +38,7 @@ PG_TUNE_K3_ANCHORS = 20         # packed coverage pass anchors per tile and refe
 PG_TUNE_FREQ_FORM = 21          # pg_freq's accumulate pass: 0 aggregated in the wave, 1 every lane its own atomics
 PG_TUNE_CMP_CHUNK = 22          # pg_freq_compare's shared pass: label-axis words per block (0 = by size)
 PG_TUNE_CMP_FORM = 23           # pg_freq_compare's curve pass: 0 LDS counters up to 2048 genomes, 1 global atomics
+PG_TUNE_RDBG_KEYS = 24          # 0 the range pass counts rdBG members, keys swept from the table on export; 1 keys written by the build
 
 
 class PgStats(C.Structure):

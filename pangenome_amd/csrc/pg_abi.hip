@@ -397,6 +397,10 @@ int pg_tune(pg_ctx* x, int what, int64_t value) {
         if (value < 0 || value > 1) throw pg::Error(PG_EINVAL, "pg_tune: curve pass form must be 0 or 1");
         x->c.cmp_form = (int)value;
         break;
+      case PG_TUNE_RDBG_KEYS:
+        if (value < 0 || value > 1) throw pg::Error(PG_EINVAL, "pg_tune: rdBG keys form must be 0 or 1");
+        x->c.rdbg_keys = (int)value;
+        break;
       case PG_TUNE_STAGE_SLOTS:
         if (value < 0 || value == 1 || value > 8) throw pg::Error(PG_EINVAL, "pg_tune: staging slots must be 0 or 2..8");
         x->c.stage_slots = value ? (uint64_t)value : 4;

@@ -2193,9 +2193,13 @@ __global__ void k_snap(const unsigned long long* __restrict__ cursor, unsigned l
 // zeroes the LDS copy for the block's next partition.
 // Persistent: block b takes partitions b, b + G, ...; the records of the next
 // partition are loaded into registers before the current one is merged, so
-// their latency hides behind the merge and the pass.  Each block appends its
-// rdBG members to its own output segment (no global atomics at all) and
-// leaves its key / dBG / member counts in its own counter slot.
+// their latency hides behind the merge and the pass.  Each block leaves its
+// key / dBG / member counts in its own counter slot (no global atomics at
+// all).  The members' keys are not kept: the table's mask words say which
+// keys are members, and export_rdbg sweeps them out on demand, as export_dbg
+// does the dBG.  (The eager form, PG_TUNE_RDBG_KEYS 1, also appends each
+// block's member keys to its own output segment, for a caller that exports
+// after every build of a table too large to sweep each time.)
 constexpr int RB_T = 512;                     // 2 blocks (16 waves) per CU: 70 KiB of LDS each
 constexpr int RB_R = 8;                       // records per thread and partition held in registers
 // <= 4096 buckets (64 KiB of LDS) per partition (2048-bucket partitions at 3
@@ -2267,22 +2271,28 @@ __device__ __forceinline__ uint64_t part_count(const Recs& I, uint32_t f, uint32
 // vmcnt 0, expcnt 7, lgkmcnt 15)
 __device__ __forceinline__ void wait_vm() { __builtin_amdgcn_s_waitcnt(0x0F70); }
 
-template <bool NT>
+// KEYS: the eager form (pg_tune PG_TUNE_RDBG_KEYS 1) also writes the members'
+// keys to R.keys.  The default only counts them - each lane adds the member
+// bits of its words to a register - and export_rdbg sweeps the table for the
+// keys (k_export_rdbg); s_mcur, s_mq and R.keys are then never referenced.
+template <bool NT, bool KEYS>
 __global__ void __launch_bounds__(RB_T, 4)
 k_build_range(Recs I, TableView T, uint32_t rbits, uint32_t nparts, RdbgOut R, unsigned* __restrict__ flags) {
   __shared__ unsigned long long W[2 << RANGE_BITS];
   __shared__ unsigned long long OK[OVL];      // h + 1, 0 = empty
   __shared__ uint32_t OM[OVL];
-  __shared__ unsigned long long s_mcur;       // this block's members so far
-  __shared__ unsigned long long s_mq[RB_T / 64][MQ];   // per-wave member queue
-  __shared__ unsigned long long s_red[2][RB_T / 64];
+  __shared__ unsigned long long s_mcur;       // (KEYS) this block's members so far
+  __shared__ unsigned long long s_mq[RB_T / 64][MQ];   // (KEYS) per-wave member queue
+  __shared__ unsigned long long s_red[3][RB_T / 64];
   const uint32_t rng = 1u << rbits, G = gridDim.x;
   const uint64_t qmask = (1ull << T.qbits) - 1ull;
   uint32_t z = 0;
   asm volatile("" : "+v"(z));
   for (uint32_t i = threadIdx.x; i < 2 * rng; i += RB_T) W[i] = 0ull;
   for (uint32_t i = threadIdx.x; i < OVL; i += RB_T) { OK[i] = 0ull; OM[i] = 0u; }
-  if (threadIdx.x == 0) s_mcur = 0ull;
+  if constexpr (KEYS) {
+    if (threadIdx.x == 0) s_mcur = 0ull;
+  }
   uint32_t f = blockIdx.x;
   unsigned long long ch[RB_R], nh[RB_R];
   uint32_t cm[RB_R], nm[RB_R];
@@ -2318,15 +2328,16 @@ k_build_range(Recs I, TableView T, uint32_t rbits, uint32_t nparts, RdbgOut R, u
   // iteration wait for its own prefetch right after issuing it), and at the
   // end, behind the range's stores.
   wait_vm();
-  uint32_t created = 0, ndbg = 0;
+  uint32_t created = 0, ndbg = 0, nmem = 0;                    // nmem: (!KEYS) this lane's rdBG members
   const uint64_t mseg = (uint64_t)blockIdx.x * R.cap;
-  // rdBG members: each wave queues h (| 1 << 63 for the rc orientation) in its
-  // own LDS buffer and turns a full buffer into keys with all 64 lanes busy
-  // (unperm + rc cost ~250 VALU per wave: run per bucket, nearly every wave
-  // paid them for a handful of member lanes)
+  // rdBG members, KEYS: each wave queues h (| 1 << 63 for the rc orientation)
+  // in its own LDS buffer and turns a full buffer into keys with all 64 lanes
+  // busy (unperm + rc cost ~250 VALU per wave: run per bucket, nearly every
+  // wave paid them for a handful of member lanes)
   const uint32_t lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
   uint32_t mp = 0;                                             // queued in this wave's buffer (wave-uniform)
-  auto flush = [&]() {
+  // (these three are called, and so exist, only in the KEYS form)
+  [[maybe_unused]] auto flush = [&]() {
     if (!mp) return;
     unsigned long long base = 0;
     if (lane == 0) base = atomicAdd(&s_mcur, (unsigned long long)mp);
@@ -2340,7 +2351,7 @@ k_build_range(Recs I, TableView T, uint32_t rbits, uint32_t nparts, RdbgOut R, u
     }
     mp = 0;
   };
-  auto push1 = [&](unsigned long long e, bool on) {
+  [[maybe_unused]] auto push1 = [&](unsigned long long e, bool on) {
     const unsigned long long bal = __ballot(on);
     const uint32_t n = (uint32_t)__builtin_popcountll(bal);
     if (!n) return;
@@ -2349,7 +2360,7 @@ k_build_range(Recs I, TableView T, uint32_t rbits, uint32_t nparts, RdbgOut R, u
     if (on) s_mq[wv][mp + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u))] = e;
     mp += n;
   };
-  auto push = [&](uint64_t h, uint32_t mb) {                   // every lane of the wave calls it
+  [[maybe_unused]] auto push = [&](uint64_t h, uint32_t mb) {  // every lane of the wave calls it
     push1(h, mb & 1u);
     push1(h | (1ull << 63), mb & 2u);
   };
@@ -2388,13 +2399,16 @@ k_build_range(Recs I, TableView T, uint32_t rbits, uint32_t nparts, RdbgOut R, u
         ovf_or(T, T.unperm(kk - 1ull), m, flags + 4);
         ++created;
         ndbg += ((m >> 12) & 1u) + ((m >> 25) & 1u);
+        if constexpr (!KEYS) nmem += (uint32_t)__builtin_popcount(member_bits(m));
         OK[i] = 0ull;
         OM[i] = 0u;
       }
-      push(kk - 1ull, kk ? member_bits(m) : 0u);
+      if constexpr (KEYS) push(kk - 1ull, kk ? member_bits(m) : 0u);
     }
     const uint64_t b0 = (uint64_t)f << rbits;
-    for (uint32_t i0 = 0; i0 < rng; i0 += RB_T) {              // every lane runs every trip (wave scans)
+    // (KEYS: every lane runs every trip, for the wave scans of push; the
+    // count-only form has no wave-wide operation, and a lane stops at rng)
+    for (uint32_t i0 = 0; KEYS ? i0 < rng : i0 + threadIdx.x < rng; i0 += RB_T) {
       const uint32_t i = i0 + threadIdx.x;
       const bool live = i < rng;
       const unsigned long long x = live ? W[2 * i] : 0ull, y = live ? W[2 * i + 1] : 0ull;
@@ -2406,10 +2420,13 @@ k_build_range(Recs I, TableView T, uint32_t rbits, uint32_t nparts, RdbgOut R, u
       const uint32_t mx = (uint32_t)(x & MW_MASK), my = (uint32_t)(y & MW_MASK);
       created += (x ? 1u : 0u) + (y ? 1u : 0u);
       ndbg += ((mx >> 12) & 1u) + ((mx >> 25) & 1u) + ((my >> 12) & 1u) + ((my >> 25) & 1u);
-      const uint32_t bx = x ? member_bits(mx) : 0u, by = y ? member_bits(my) : 0u;
-      if (!(PG_EXP_BITS & 8)) {
+      // (an empty word has no presence bit: member_bits(0) == 0)
+      const uint32_t bx = member_bits(mx), by = member_bits(my);
+      if constexpr (KEYS) {
         push(((b0 + i) << T.qbits) | (x >> MW_BITS), bx);
         push(((b0 + i) << T.qbits) | (y >> MW_BITS), by);
+      } else {
+        nmem += (uint32_t)__builtin_popcount(bx | (by << 2));
       }
     }
     __syncthreads();
@@ -2419,19 +2436,28 @@ k_build_range(Recs I, TableView T, uint32_t rbits, uint32_t nparts, RdbgOut R, u
     n_cur = n_nxt;
     n_nxt = n_nn;
   }
-  flush();
-  // the block's counters
-  unsigned long long a = created, b = ndbg;
-  for (int o = 32; o > 0; o >>= 1) { a += __shfl_down(a, o, 64); b += __shfl_down(b, o, 64); }
-  if ((threadIdx.x & 63) == 0) { s_red[0][threadIdx.x >> 6] = a; s_red[1][threadIdx.x >> 6] = b; }
+  if constexpr (KEYS) flush();
+  // the block's counters (a block without a partition reports zeros)
+  unsigned long long a = created, b = ndbg, m = nmem;
+  for (int o = 32; o > 0; o >>= 1) {
+    a += __shfl_down(a, o, 64);
+    b += __shfl_down(b, o, 64);
+    m += __shfl_down(m, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    s_red[0][threadIdx.x >> 6] = a;
+    s_red[1][threadIdx.x >> 6] = b;
+    s_red[2][threadIdx.x >> 6] = m;
+  }
   __syncthreads();
   if (threadIdx.x == 0) {
-    unsigned long long sa = 0, sb = 0;
-    for (int w = 0; w < RB_T / 64; ++w) { sa += s_red[0][w]; sb += s_red[1][w]; }
+    unsigned long long sa = 0, sb = 0, sm = 0;
+    for (int w = 0; w < RB_T / 64; ++w) { sa += s_red[0][w]; sb += s_red[1][w]; sm += s_red[2][w]; }
     unsigned long long* o = R.ctr + (uint64_t)blockIdx.x * RB_CTR;
     o[0] = sa;
     o[1] = sb;
-    o[2] = s_mcur;
+    if constexpr (KEYS) o[2] = s_mcur;
+    else o[2] = sm;
   }
 }
 
@@ -2512,6 +2538,48 @@ __global__ void __launch_bounds__(256) k_export_dbg(TableView T, uint64_t nw, ui
       }
       if (m[e] & PRES_B) {
         if (o < cap) { keys[o] = T.rc(c); masks[o] = (m[e] >> B_SHIFT) & MASK12; }
+        ++o;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// rdBG export after a count-only build: the same sweep over the same entry
+// index space, emitting the member orientations of every entry (member_bits
+// of its mask word: bit 0 the canonical key c, bit 1 rc(c) - what the eager
+// form's flush writes).  Unsorted; the host sorts.
+__global__ void __launch_bounds__(256) k_export_rdbg(TableView T, uint64_t nw, uint64_t ntot,
+                                                    unsigned long long* __restrict__ keys, uint64_t cap,
+                                                    unsigned long long* __restrict__ counter) {
+  __shared__ uint32_t s_scan[4];
+  __shared__ unsigned long long s_base;
+  for (uint64_t c0 = blockIdx.x * (uint64_t)(256 * EXE); c0 < ntot; c0 += (uint64_t)gridDim.x * 256 * EXE) {
+    uint32_t mb = 0, cnt = 0;                                  // 2 member bits per entry
+#pragma unroll
+    for (int e = 0; e < EXE; ++e) {
+      const uint64_t i = c0 + (uint64_t)threadIdx.x * EXE + e;
+      const uint32_t b = i < ntot ? member_bits(entry_mask(T, nw, i)) : 0u;
+      mb |= b << (2 * e);
+      cnt += (b & 1u) + (b >> 1);
+    }
+    uint32_t tot;
+    const uint32_t pre = block_excl_scan<256>(cnt, s_scan, tot);
+    if (threadIdx.x == 0) s_base = tot ? atomicAdd(counter, (unsigned long long)tot) : 0ull;
+    __syncthreads();
+    // writes past cap are dropped; the host rejects a count other than cap
+    uint64_t o = s_base + pre;
+#pragma unroll
+    for (int e = 0; e < EXE; ++e) {
+      const uint32_t b = (mb >> (2 * e)) & 3u;
+      if (!b) continue;
+      const uint64_t c = entry_key(T, nw, c0 + (uint64_t)threadIdx.x * EXE + e);
+      if (b & 1u) {
+        if (o < cap) keys[o] = c;
+        ++o;
+      }
+      if (b & 2u) {
+        if (o < cap) keys[o] = T.rc(c);
         ++o;
       }
     }
@@ -2868,6 +2936,8 @@ static bool finish_build(Ctx& c, ACount& a, bool spec, const Presplit* pre = nul
   (void)fp0;
   double capx = 1.15;
   uint64_t ovf_mult = 1;
+  // the eager form's member segments (the default keeps no member keys)
+  const bool keys = c.rdbg_keys != 0;
   double rseg_frac = c.r_ratio > 0 ? std::min(2.0, 1.5 * c.r_ratio + 0.002) : 2.0;
   // a split level that overflowed: its partitions' exact counts (the cursors
   // count every record, kept or not) size it on the next attempt, so skewed
@@ -2924,10 +2994,11 @@ static bool finish_build(Ctx& c, ACount& a, bool spec, const Presplit* pre = nul
     c.ctrS.reserve(8 * std::max<uint64_t>(ctr_words, 1));
     const uint64_t nparts = 1ull << fp;
     const uint32_t grid = (uint32_t)std::min<uint64_t>(nparts, (uint64_t)RB_PER_CU * (uint64_t)c.n_cu);   // persistent
-    const uint64_t rcap = (uint64_t)(rseg_frac * (double)a.total / grid) + 4096;
-    c.rseg.reserve(8 * grid * rcap);
+    const uint64_t rcap = keys ? (uint64_t)(rseg_frac * (double)a.total / grid) + 4096 : 0;
+    if (keys) c.rseg.reserve(8 * grid * rcap);
+    else c.rseg.release();
     c.rseg_cap = rcap;
-    c.rseg_nseg = grid;
+    c.rseg_nseg = keys ? grid : 0;
     c.k5_ctr.reserve(8 * RB_CTR * grid);
     FillList fl;
     fl.add(c.ovf.p, sizeof(Slot) * ovf);
@@ -2969,10 +3040,13 @@ static bool finish_build(Ctx& c, ACount& a, bool spec, const Presplit* pre = nul
     }
     c.split_passes = use_pre ? 0 : (int)lv.size();
     unsigned long long* k5 = c.k5_ctr.as<unsigned long long>();
-    const RdbgOut ro{c.rseg.as<unsigned long long>(), k5, rcap};
+    const RdbgOut ro{keys ? c.rseg.as<unsigned long long>() : nullptr, k5, rcap};
+    const bool nt = a.total < SPLIT_NT_MAX;
     c.t6.start(c.stream);
-    hipLaunchKernelGGL(a.total < SPLIT_NT_MAX ? k_build_range<true> : k_build_range<false>, dim3(grid), dim3(RB_T), 0,
-                       c.stream, in, c.tv, rbits, (uint32_t)nparts, ro, c.flags.as<unsigned>());
+    hipLaunchKernelGGL(keys ? (nt ? k_build_range<true, true> : k_build_range<false, true>)
+                            : (nt ? k_build_range<true, false> : k_build_range<false, false>),
+                       dim3(grid), dim3(RB_T), 0, c.stream, in, c.tv, rbits, (uint32_t)nparts, ro,
+                       c.flags.as<unsigned>());
     PG_HIP(hipGetLastError());
     c.t6.stop(c.stream);
     // one readback: stage C's counters, the flags, (spec) stage A's cursors
@@ -3041,19 +3115,20 @@ static bool finish_build(Ctx& c, ACount& a, bool spec, const Presplit* pre = nul
       throw Error(-12, "build: LDS overflow set full at the largest table");
     }
     if (bits & F_OVF_FULL) { ovf_mult *= 4; continue; }
-    if (bits & F_RSEG_OVER) { rseg_frac = 2.0; continue; }
+    if (bits & F_RSEG_OVER) { rseg_frac = 2.0; continue; }   // (the eager form only)
     uint64_t created = 0, ndbg = 0, nr = 0;
-    c.rseg_cnt.resize(grid);
+    c.rseg_cnt.resize(keys ? grid : 0);
     for (uint32_t b = 0; b < grid; ++b) {
       created += h[RB_CTR * b];
       ndbg += h[RB_CTR * b + 1];
-      c.rseg_cnt[b] = h[RB_CTR * b + 2];
-      nr += c.rseg_cnt[b];
+      nr += h[RB_CTR * b + 2];
+      if (keys) c.rseg_cnt[b] = h[RB_CTR * b + 2];
     }
     c.n_canon = created;
     c.n_dbg = ndbg + c.sentinel;
     c.n_rdbg = nr + c.sentinel;               // key 2^64-1, mask 32: always an rdBG member
     c.r_ratio = a.total ? (double)nr / (double)a.total : 0.0;
+    c.rseg_built = keys;
     c.built = c.reduced = true;
     c.early_split_used = use_pre;
     ++c.build_gen;
@@ -3470,9 +3545,54 @@ uint64_t export_dbg(Ctx& c, uint64_t* h_keys, uint16_t* h_masks, uint64_t cap) {
   return total;
 }
 
+// n unsorted rdBG keys on the device -> h_keys, sorted on the device first
+static void rdbg_keys_out(Ctx& c, DevBuf& in, uint64_t n, uint64_t* h_keys) {
+  DevBuf k2, tmp;
+  k2.reserve(8 * n);
+  size_t bytes = 0;
+  PG_HIP(rocprim::radix_sort_keys(nullptr, bytes, in.as<unsigned long long>(), k2.as<unsigned long long>(), (size_t)n,
+                                  0, c.kb, c.stream));
+  tmp.reserve(bytes + 16);
+  bytes = tmp.cap;
+  PG_HIP(rocprim::radix_sort_keys(tmp.p, bytes, in.as<unsigned long long>(), k2.as<unsigned long long>(), (size_t)n, 0,
+                                  c.kb, c.stream));
+  PG_HIP(hipMemcpyAsync(h_keys, k2.p, 8 * n, hipMemcpyDeviceToHost, c.stream));
+  c.sync();
+}
+
+// After a count-only build (the default) the keys come out of the table: one
+// sweep of every primary word and overflow slot, then the sort.  The sweep
+// must find exactly the build's count.
+static void export_rdbg_sweep(Ctx& c, uint64_t* h_keys) {
+  const uint64_t n = c.n_rdbg - c.sentinel;
+  if (n) {
+    const uint64_t ntot = 2 * c.cap + c.ovf_cap;
+    DevBuf out, cnt;
+    out.reserve(8 * n);
+    cnt.reserve(8);
+    PG_HIP(hipMemsetAsync(cnt.p, 0, 8, c.stream));
+    hipLaunchKernelGGL(k_export_rdbg, dim3(grid_for(ntot, 256 * EXE, 8192)), dim3(256), 0, c.stream, c.tv, 2 * c.cap,
+                       ntot, out.as<unsigned long long>(), n, cnt.as<unsigned long long>());
+    PG_HIP(hipGetLastError());
+    unsigned long long found = 0;
+    PG_HIP(hipMemcpyAsync(&found, cnt.p, 8, hipMemcpyDeviceToHost, c.stream));
+    c.sync();
+    if (found != n) {
+      out.release(); cnt.release();
+      throw Error(-5, "export_rdbg: the table holds " + std::to_string(found) + " rdBG members, the build counted " +
+                          std::to_string(n));
+    }
+    rdbg_keys_out(c, out, n, h_keys);
+    out.release(); cnt.release();
+  }
+  if (c.sentinel) h_keys[n] = SENTINEL;
+}
+
 uint64_t export_rdbg(Ctx& c, uint64_t* h_keys, uint64_t cap) {
   if (!c.reduced) throw Error(-22, "export_rdbg: no rdBG (call pg_build_rdbg first)");
-  if (h_keys && cap >= c.n_rdbg) {
+  if (h_keys && cap >= c.n_rdbg && !c.rseg_built) {
+    export_rdbg_sweep(c, h_keys);
+  } else if (h_keys && cap >= c.n_rdbg) {
     // the blocks' segments gathered on the device into one run, one copy back
     const uint64_t nseg = c.rseg_nseg, n = c.n_rdbg - c.sentinel;
     std::vector<unsigned long long> off(nseg + 1, 0);
@@ -3487,17 +3607,7 @@ uint64_t export_rdbg(Ctx& c, uint64_t* h_keys, uint64_t cap) {
       hipLaunchKernelGGL(k_gather_segs, dim3((unsigned)nseg), dim3(256), 0, c.stream, c.rseg.as<unsigned long long>(),
                          c.rseg_cap, d_off.as<unsigned long long>(), out.as<unsigned long long>());
       PG_HIP(hipGetLastError());
-      DevBuf k2, tmp;                                   // sorted on the device
-      k2.reserve(8 * n);
-      size_t bytes = 0;
-      PG_HIP(rocprim::radix_sort_keys(nullptr, bytes, out.as<unsigned long long>(), k2.as<unsigned long long>(),
-                                      (size_t)n, 0, c.kb, c.stream));
-      tmp.reserve(bytes + 16);
-      bytes = tmp.cap;
-      PG_HIP(rocprim::radix_sort_keys(tmp.p, bytes, out.as<unsigned long long>(), k2.as<unsigned long long>(),
-                                      (size_t)n, 0, c.kb, c.stream));
-      PG_HIP(hipMemcpyAsync(h_keys, k2.p, 8 * n, hipMemcpyDeviceToHost, c.stream));
-      c.sync();
+      rdbg_keys_out(c, out, n, h_keys);
     }
     c.sync();
     d_off.release();

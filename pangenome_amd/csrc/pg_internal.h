@@ -242,10 +242,14 @@ struct Ctx {
   // for (at table bits lv_keep_bb): later builds' plans start from them
   std::vector<uint64_t> lv_keep;
   int lv_keep_bb = -1;
-  DevBuf rseg;                        // rdBG keys: one segment of rseg_cap per stage C block
+  // rdBG keys.  By default a build only counts the members and export_rdbg
+  // sweeps the table; the eager form keeps each stage C block's member keys
+  int rdbg_keys = 0;                  // pg_tune: 0 = count in the range pass, keys from the table on export; 1 = eager
+  bool rseg_built = false;            // the last build was eager: rseg / rseg_cnt hold its keys
+  DevBuf rseg;                        // (eager) rdBG keys: one segment of rseg_cap per stage C block
   DevBuf k5_ctr;                      // per stage C block: key / dBG / member counts
   uint64_t rseg_cap = 0, rseg_nseg = 0;
-  std::vector<uint64_t> rseg_cnt;     // members per segment
+  std::vector<uint64_t> rseg_cnt;     // (eager) members per segment
   uint64_t n_records_a = 0;           // stage A records of the last build
   double u_ratio = 0, r_ratio = 0;    // last build: records per forward window, rdBG keys per record
 

@@ -55,6 +55,9 @@ tests use an oracle-backed stand-in with the same methods):
                                     their occurrence counts
   partition / merge / build_rdbg    the exchange (exchange_and_reduce)
   owner_rdbg() -> keys              the owner partition's rdBG keys
+  keep_rdbg_keys(on)                optional: later merges write their rdBG keys
+                                    as they count them (a loop that exports
+                                    after every merge sets it; see GpuShard)
   members(keys, n_records, rc0)     the global rdBG as walk membership
   edges(flags, rc1) -> (tuples, counts, walk)   first-occurrence order
   rows_text(labels, flags, rc1, names) -> bytes
@@ -838,24 +841,34 @@ def _stream_routed(shard, world: int, rank: int, device, chunks, n_records: int,
     n_dbg_loc = n_rdbg_loc = 0
     keys = []
     t0 = lap("flag", t0)
-    for p in range(P):
-        _fence(device, shard)
-        shard.route_merge_segs(segs[p], nparts, sentinel=sent_global and rank == 0 and p == 0)
-        rows, sm = shard.merge_check()
-        if rows != logn[p] or (sm & M64) != logsum[p]:
-            fail.append("exchange: rank %d's final merge of sub-log %d read %d records with sum %#x, the log holds %d "
-                        "with sum %#x (stage: merge)" % (rank, p, rows, sm & M64, logn[p], logsum[p]))
-        st = shard.build_rdbg()
-        n_dbg_loc += int(st.n_dbg)
-        n_rdbg_loc += int(st.n_rdbg)
-        if lib is not None:
-            lib["merges"].append(dict(rebin_ms=st.ms_insert, split_ms=st.ms_split, range_ms=st.ms_range,
-                                      records=int(logn[p]), buckets=int(st.table_capacity), n_rdbg=int(st.n_rdbg),
-                                      split_passes=int(st.build_flags) >> 16 & 255))
-        t0 = lap("merge", t0)
-        if want_keys:
-            keys.append(np.ascontiguousarray(shard.owner_rdbg(), dtype=np.uint64))
-            t0 = lap("keys", t0)
+    # every sub-log's keys are exported right after its merge: have the merges
+    # write them (a sweep of a 2^30-bucket table per sub-log costs more than
+    # the writes); counts alone take the default
+    eager = getattr(shard, "keep_rdbg_keys", None) if want_keys else None
+    if eager:
+        eager(True)
+    try:
+        for p in range(P):
+            _fence(device, shard)
+            shard.route_merge_segs(segs[p], nparts, sentinel=sent_global and rank == 0 and p == 0)
+            rows, sm = shard.merge_check()
+            if rows != logn[p] or (sm & M64) != logsum[p]:
+                fail.append("exchange: rank %d's final merge of sub-log %d read %d records with sum %#x, the log holds "
+                            "%d with sum %#x (stage: merge)" % (rank, p, rows, sm & M64, logn[p], logsum[p]))
+            st = shard.build_rdbg()
+            n_dbg_loc += int(st.n_dbg)
+            n_rdbg_loc += int(st.n_rdbg)
+            if lib is not None:
+                lib["merges"].append(dict(rebin_ms=st.ms_insert, split_ms=st.ms_split, range_ms=st.ms_range,
+                                          records=int(logn[p]), buckets=int(st.table_capacity),
+                                          n_rdbg=int(st.n_rdbg), split_passes=int(st.build_flags) >> 16 & 255))
+            t0 = lap("merge", t0)
+            if want_keys:
+                keys.append(np.ascontiguousarray(shard.owner_rdbg(), dtype=np.uint64))
+                t0 = lap("keys", t0)
+    finally:
+        if eager:
+            eager(False)
     del bufs
     sums = torch.tensor([n_dbg_loc, n_rdbg_loc, 1 if fail else 0], dtype=torch.int64, device=comm)
     dist.all_reduce(sums, op=dist.ReduceOp.SUM, group=group)
@@ -1101,6 +1114,13 @@ class GpuShard:
 
     def owner_rdbg(self):
         return self.ctx.rdbg()
+
+    def keep_rdbg_keys(self, on):
+        """Later builds and merges write their rdBG keys as they count them
+        (PG_TUNE_RDBG_KEYS 1) instead of leaving them to a sweep of the table
+        in owner_rdbg: for a loop that exports after every merge."""
+        from . import _lib
+        self.ctx.tune(_lib.PG_TUNE_RDBG_KEYS, 1 if on else 0)
 
     def members(self, keys, n_records, rc0):
         self.ctx.dbg_load(keys, None, None)

@@ -6,8 +6,9 @@
 
 Each --tune argument is one variant (a comma-separated list of pg_tune
 settings by PG_TUNE_* name, or "base" for none).  Prints per variant the
-median step, stage A / split / range spans (HIP events), stage A records, and
-whether every step's counts match the oracle digest of c3a."""
+median, smallest and largest step, stage A / split / range spans (HIP
+events), stage A records, and whether every step's counts match the oracle
+digest of c3a; with --json, every step's wall time per variant as one JSON line."""
 import argparse
 import json
 import os
@@ -28,6 +29,7 @@ def main():
     ap.add_argument("--tune", action="append", default=[])
     ap.add_argument("--host", action="store_true", help="pg_build_host from the page-cache-warm mmap instead")
     ap.add_argument("--alt", action="store_true", help="alternate two batches (genomes 0-99, 100-199), as bench.py does")
+    ap.add_argument("--json", action="store_true", help="also print every step's ms per variant as one JSON line")
     ap.add_argument("--env", action="append", default=[], help="per-variant environment NAME=V (index-aligned with --tune)")
     args = ap.parse_args()
     import torch
@@ -83,9 +85,12 @@ def main():
     for vi, v in enumerate(variants):
         a = np.array([r[:6] for r in res[vi]])
         med = np.median(a, axis=0)
-        print("%-40s step %.3f (max %.3f)  parse %.3f  stageA %.3f  split %.3f  range %.3f  recA %d  ok %s" %
-              (v + (" " + args.env[vi] if vi < len(args.env) else ""), med[0], a[:, 0].max(), med[1], med[2],
+        print("%-40s step %.3f (min %.3f max %.3f)  parse %.3f  stageA %.3f  split %.3f  range %.3f  recA %d  ok %s" %
+              (v + (" " + args.env[vi] if vi < len(args.env) else ""), med[0], a[:, 0].min(), a[:, 0].max(), med[1], med[2],
                med[3], med[4], int(med[5]), all(r[6] for r in res[vi])), flush=True)
+    if args.json:
+        print(json.dumps({"ab_k3_steps_ms": {v: [round(r[0], 4) for r in res[vi]] for vi, v in enumerate(variants)},
+                          "range_ms": {v: [round(r[4], 4) for r in res[vi]] for vi, v in enumerate(variants)}}))
 
 
 if __name__ == "__main__":
