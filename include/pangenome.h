@@ -279,7 +279,8 @@ int pg_labels_from_edges(pg_ctx* ctx, const uint64_t* tuples, uint64_t n_edges, 
                          const int64_t* mcl_value, const int64_t* mcl_label, uint64_t n_mcl, int64_t next_label,
                          uint64_t* n_labels);
 /* The label table in insertion order: the .mcl entries, then the new ones
- * by label (cap >= n_labels). */
+ * by label (cap >= n_labels); after the last pg_cluster_cc or
+ * pg_cluster_markov, the nodes in file order with their line indices. */
 int pg_labels_export(pg_ctx* ctx, int64_t* key, int64_t* value, int64_t* label, uint64_t cap);
 
 /* ---- built-in clustering of the `.xyz` graph (reference README step 4:
@@ -334,9 +335,76 @@ int pg_cluster_cc(pg_ctx* ctx, const uint64_t* tuples, const int64_t* counts, ui
 int pg_cluster_sweep(pg_ctx* ctx, const uint64_t* tuples, const int64_t* counts, uint64_t n_edges,
                      const int64_t* thresholds, uint64_t n_thr, uint64_t* n_nodes, int64_t* max_weight,
                      uint64_t* edges, uint64_t* clusters, uint64_t* largest, uint64_t* singletons);
-/* The `.mcl` text of the last pg_cluster_cc (kept on the device).  out ==
- * NULL: only *n_bytes (the size) is set; otherwise cap >= that size, else
- * PG_ERANGE.  PG_EINVAL before any pg_cluster_cc. */
+/* ---- Markov clustering (MCL) of the `.xyz` graph: the clusters come from flow
+ *      instead of a threshold.  Our own MCL in 31-bit fixed point: integer only,
+ *      the result depends on the input alone.  It is not bit-identical to the
+ *      external `mcl` program, whose pruning scheme and loop weights differ.
+ * Constants: ONE = 2^31, CUT = ONE / 10000, STOP = ONE / 1000; every value is
+ * an unsigned integer, >> and / are floor operations.
+ * Parameters: min_weight >= 1; inflation2 in [3, 40], the inflation being
+ * r = inflation2 / 2 (3: mcl's -I 1.5); select in [1, 64]; max_iter in
+ * [0, 10000].
+ * Nodes: exactly pg_cluster_cc's (ids by first appearance, the same limits).
+ * Weights: for nodes i != j, w(i, j) = the summed counts of all listed edges
+ * between them, in either direction, whose count is >= min_weight (symmetric).
+ * Self-loops in the list and lighter edges add nothing, but their ends are
+ * nodes.  A summed weight >= 2^32 is PG_ERANGE.  Every node j gets a loop
+ * w(j, j) = the largest w(i, j) of its column, or 1 without an edge.
+ * prune(f, select) of a column's positive values f[i]: n[i] = (f[i] << 31) /
+ * sum f; the entries ordered by n descending, then by row ascending; the first
+ * is kept always, of the rest in that order those with n >= CUT, at most
+ * select - 1 of them; the stored value is (n[i] << 31) / sum n[kept], in
+ * [1, ONE]; entries are stored by row ascending.
+ * Initial matrix: column j = prune of its weights.
+ * One iteration, for every column j of the previous matrix M:
+ *   expansion  acc[i] = sum over the stored k of column j of M[i,k] * M[k,j]
+ *              (exact 64-bit products, the sum below 2^62); e[i] = acc[i] >> 31
+ *   scaling    x[i] = (e[i] << 31) / max e (the largest becomes ONE, so the
+ *              inflation never empties a column)
+ *   inflation  y = ONE; y = (y * x) >> 31, inflation2 / 2 times; inflation2
+ *              odd: y = (y * isqrt(x << 31)) >> 31 with the exact integer
+ *              root; entries with y == 0 are dropped
+ *   new column prune(y, select)
+ *   chaos_j    max v - ((sum v^2) >> 31) over the new column's values v
+ * Stopping: chaos = the largest chaos_j; the iteration stops when chaos <=
+ * STOP or after max_iter iterations.  max_iter == 0 gives the initial matrix
+ * with its chaos computed the same way.  No edges: 0 iterations, chaos 0.
+ * Clusters: nodes i and j are joined for every stored entry M[i, j] of the last
+ * matrix; the clusters are the components.  Their order, the member order, the
+ * `.mcl` text and the label table are exactly pg_cluster_cc's, in the same
+ * slot: pg_clusters_format[_fd] and pg_labels_export serve either clusterer.
+ * tuples == NULL: the last pg_edges where it lies on the device.
+ * *n_clusters, *n_nodes, *n_iter (the iterations run), *chaos (the last
+ * matrix's): each may be NULL.
+ * PG_EINVAL before any device work, the previous clustering, text and label
+ * table kept: pg_cluster_cc's list, or a parameter outside its range.
+ * PG_ERANGE (2^32 nodes or more, a weight sum) and PG_ENOMEM on an allocation
+ * failure of the matrices keep the previous result too.
+ * Device memory: two matrices of (8 x select + 4) x U bytes while the call
+ * runs (U nodes); the final one is kept, see pg_cluster_markov_matrix. */
+int pg_cluster_markov(pg_ctx* ctx, const uint64_t* tuples, const int64_t* counts, uint64_t n_edges,
+                      int64_t min_weight, uint32_t inflation2, uint32_t select, uint32_t max_iter,
+                      uint64_t* n_clusters, uint64_t* n_nodes, uint32_t* n_iter, uint64_t* chaos);
+/* The final matrix of the last pg_cluster_markov, for tests (max_iter = 0, 1,
+ * 2 pin the weights, the expansion, the inflation and the pruning apart):
+ * col_len[U] the column lengths, rows and vals [U x select] with each column's
+ * entries by row ascending and 0 behind them, *select (may be NULL) the stride.
+ * The context keeps that matrix, 8 x U x select + 4 x U device bytes, until the
+ * next clustering call (pg_cluster_cc or pg_cluster_markov) or pg_destroy.
+ * PG_EINVAL before any pg_cluster_markov (or after a later pg_cluster_cc);
+ * PG_ERANGE if cap_nodes < U. */
+int pg_cluster_markov_matrix(pg_ctx* ctx, uint32_t* col_len, uint32_t* rows, uint32_t* vals, uint64_t cap_nodes,
+                             uint32_t* select);
+/* Sizes of the last pg_cluster_markov (each pointer may be NULL): U, the
+ * stride, and the columns its iterations ran in each size class, summed over
+ * the iterations: a wave with a small table (a bound of at most 128
+ * candidates), a block with a middle one (at most 1024) and a block with the
+ * table for select^2.  PG_EINVAL as pg_cluster_markov_matrix. */
+int pg_cluster_markov_stats(pg_ctx* ctx, uint64_t* n_nodes, uint32_t* select, uint64_t* cols_wave,
+                            uint64_t* cols_mid, uint64_t* cols_block);
+/* The `.mcl` text of the last pg_cluster_cc or pg_cluster_markov (kept on the
+ * device).  out == NULL: only *n_bytes (the size) is set; otherwise cap >=
+ * that size, else PG_ERANGE.  PG_EINVAL before any of the two. */
 int pg_clusters_format(pg_ctx* ctx, char* out, uint64_t cap, uint64_t* n_bytes);
 /* The same text written to descriptor fd, as pg_edges_format_fd writes. */
 int pg_clusters_format_fd(pg_ctx* ctx, int fd, uint64_t* n_bytes);

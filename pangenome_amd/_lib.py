@@ -99,6 +99,10 @@ SIGNATURES = {
     "pg_labels_from_edges": (C.c_int, [_P, _P, C.c_uint64, _P, _P, _P, C.c_uint64, C.c_int64, _U64P]),
     "pg_labels_export": (C.c_int, [_P, _P, _P, _P, C.c_uint64]),
     "pg_cluster_cc": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int64, _U64P, _U64P]),
+    "pg_cluster_markov": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int64, C.c_uint32, C.c_uint32, C.c_uint32, _U64P, _U64P,
+                                    C.POINTER(C.c_uint32), _U64P]),
+    "pg_cluster_markov_matrix": (C.c_int, [_P, _P, _P, _P, C.c_uint64, C.POINTER(C.c_uint32)]),
+    "pg_cluster_markov_stats": (C.c_int, [_P, _U64P, C.POINTER(C.c_uint32), _U64P, _U64P, _U64P]),
     "pg_cluster_sweep": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint64, _U64P, _I64P, _P, _P, _P, _P]),
     "pg_clusters_format": (C.c_int, [_P, _P, C.c_uint64, _U64P]),
     "pg_clusters_format_fd": (C.c_int, [_P, C.c_int, _U64P]),
@@ -570,6 +574,49 @@ class Context:
         self.n_labels = nu.value
         self.label_gen = getattr(self, "label_gen", 0) + 1
         return nc.value, nu.value
+
+    def cluster_markov(self, tuples=None, counts=None, min_weight: int = 1, inflation2: int = 3, select: int = 64,
+                       max_iter: int = 200):
+        """Markov clustering (pg_cluster_markov; host.cluster_markov is its
+        specification): inflation inflation2 / 2, columns pruned to `select`
+        entries, at most max_iter iterations.  tuples None: the last edges()
+        pass on the device.  The result takes cluster_cc's place (clusters_text,
+        labels); returns (n_clusters, n_nodes, n_iter, chaos)."""
+        nc, nu, ni, ch = C.c_uint64(), C.c_uint64(), C.c_uint32(), C.c_uint64()
+        t = None if tuples is None else np.ascontiguousarray(tuples, dtype=np.uint64).reshape(-1, 4)
+        cn = None if counts is None else np.ascontiguousarray(counts, dtype=np.int64)
+        if t is not None and cn is not None and cn.shape[0] != t.shape[0]:
+            raise ValueError("cluster_markov: %d tuples, %d counts" % (t.shape[0], cn.shape[0]))
+        for name, v in (("inflation2", inflation2), ("select", select), ("max_iter", max_iter)):
+            if not 0 <= int(v) < 2 ** 32:
+                raise ValueError("cluster_markov: %s = %d" % (name, int(v)))
+        check(self.lib.pg_cluster_markov(self.h, ptr(t), ptr(cn), 0 if t is None else t.shape[0], int(min_weight),
+                                         int(inflation2), int(select), int(max_iter), C.byref(nc), C.byref(nu),
+                                         C.byref(ni), C.byref(ch)), "pg_cluster_markov")
+        self.n_labels = nu.value
+        self.label_gen = getattr(self, "label_gen", 0) + 1
+        self.mk_shape = (nu.value, int(select))
+        return nc.value, nu.value, ni.value, ch.value
+
+    def cluster_markov_matrix(self):
+        """The last cluster_markov's final matrix (pg_cluster_markov_matrix):
+        col_len uint32 [U], rows and vals uint32 [U, select], each column's
+        entries by row ascending, zero behind them."""
+        U, S = getattr(self, "mk_shape", (0, 1))
+        col_len, rows, vals = np.zeros(max(U, 1), np.uint32), np.zeros((max(U, 1), S), np.uint32), np.zeros((max(U, 1), S), np.uint32)
+        sel = C.c_uint32()
+        check(self.lib.pg_cluster_markov_matrix(self.h, ptr(col_len), ptr(rows), ptr(vals), U, C.byref(sel)),
+              "pg_cluster_markov_matrix")
+        return col_len[:U], rows[:U], vals[:U]
+
+    def cluster_markov_stats(self):
+        """(n_nodes, select, cols_wave, cols_mid, cols_block) of the last
+        cluster_markov: the columns its iterations ran in each size class
+        (pg_cluster_markov_stats)."""
+        nu, sel, cw, cm, cb = C.c_uint64(), C.c_uint32(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        check(self.lib.pg_cluster_markov_stats(self.h, C.byref(nu), C.byref(sel), C.byref(cw), C.byref(cm),
+                                               C.byref(cb)), "pg_cluster_markov_stats")
+        return nu.value, sel.value, cw.value, cm.value, cb.value
 
     def _sweep(self, thresholds, tuples, counts):
         """pg_cluster_sweep: (n_nodes, max_weight) and the four arrays."""

@@ -95,7 +95,7 @@ void pg_destroy(pg_ctx* x) {
                         &c.recS_mw[1], &c.ctrS, &c.snapA, &c.rseg, &c.k5_ctr, &c.tile_sched, &c.tile_desc, &c.k3_queue,
                         &c.k3_hint, &c.part_cnt, &c.tile_cnt, &c.tile_off, &c.occ, &c.edge_tab, &c.pair_tab,
                         &c.edge_out, &c.edge_exp, &c.lab_tab, &c.lab_list, &c.rows_buf, &c.xyz_off,
-                        &c.text_buf, &c.clu_text, &c.fr_tab, &c.fr_spec, &c.fr_grp, &c.fr_text,
+                        &c.text_buf, &c.clu_text, &c.mk_mat, &c.fr_tab, &c.fr_spec, &c.fr_grp, &c.fr_text,
                         &c.cmp_shared, &c.cmp_curve, &c.rg_nodes, &c.rg_links, &c.rg_paths, &c.rg_steps, &c.rg_text,
                         &c.rs_tab, &c.rs_blob, &c.preload,
                         &c.dump_cnt};
@@ -714,6 +714,49 @@ int pg_cluster_cc(pg_ctx* x, const uint64_t* tuples, const int64_t* counts, uint
   });
 }
 
+int pg_cluster_markov(pg_ctx* x, const uint64_t* tuples, const int64_t* counts, uint64_t n_edges, int64_t min_weight,
+                      uint32_t inflation2, uint32_t select, uint32_t max_iter, uint64_t* n_clusters, uint64_t* n_nodes,
+                      uint32_t* n_iter, uint64_t* chaos) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_cluster_markov: ctx is NULL");
+    if (min_weight < 1) throw pg::Error(PG_EINVAL, "pg_cluster_markov: min_weight below 1");
+    if (tuples && !counts) throw pg::Error(PG_EINVAL, "pg_cluster_markov: tuples without counts");
+    if (!tuples && counts) throw pg::Error(PG_EINVAL, "pg_cluster_markov: counts without tuples");
+    if (inflation2 < 3 || inflation2 > 40) throw pg::Error(PG_EINVAL, "pg_cluster_markov: inflation2 outside [3, 40]");
+    if (select < 1 || select > 64) throw pg::Error(PG_EINVAL, "pg_cluster_markov: select outside [1, 64]");
+    if (max_iter > 10000) throw pg::Error(PG_EINVAL, "pg_cluster_markov: max_iter above 10000");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::cluster_markov(x->c, tuples, counts, n_edges, min_weight, inflation2, select, max_iter, n_iter, chaos);
+    if (n_clusters) *n_clusters = x->c.n_clusters;
+    if (n_nodes) *n_nodes = x->c.n_clu_nodes;
+  });
+}
+
+int pg_cluster_markov_matrix(pg_ctx* x, uint32_t* col_len, uint32_t* rows, uint32_t* vals, uint64_t cap_nodes,
+                             uint32_t* select) {
+  return guard([&] {
+    if (!x || !col_len || !rows || !vals) throw pg::Error(PG_EINVAL, "pg_cluster_markov_matrix: bad arguments");
+    if (!x->c.mk_ready) throw pg::Error(PG_EINVAL, "pg_cluster_markov_matrix: no matrix (call pg_cluster_markov first)");
+    if (cap_nodes < x->c.mk_nodes) throw pg::Error(PG_ERANGE, "pg_cluster_markov_matrix: buffers too small");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::markov_matrix(x->c, col_len, rows, vals);
+    if (select) *select = x->c.mk_select;
+  });
+}
+
+int pg_cluster_markov_stats(pg_ctx* x, uint64_t* n_nodes, uint32_t* select, uint64_t* cols_wave, uint64_t* cols_mid,
+                            uint64_t* cols_block) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_cluster_markov_stats: ctx is NULL");
+    if (!x->c.mk_ready) throw pg::Error(PG_EINVAL, "pg_cluster_markov_stats: no matrix (call pg_cluster_markov first)");
+    if (n_nodes) *n_nodes = x->c.mk_nodes;
+    if (select) *select = x->c.mk_select;
+    if (cols_wave) *cols_wave = x->c.mk_cols_wave;
+    if (cols_mid) *cols_mid = x->c.mk_cols_mid;
+    if (cols_block) *cols_block = x->c.mk_cols_block;
+  });
+}
+
 int pg_cluster_sweep(pg_ctx* x, const uint64_t* tuples, const int64_t* counts, uint64_t n_edges,
                      const int64_t* thresholds, uint64_t n_thr, uint64_t* n_nodes, int64_t* max_weight,
                      uint64_t* edges, uint64_t* clusters, uint64_t* largest, uint64_t* singletons) {
@@ -735,7 +778,7 @@ int pg_cluster_sweep(pg_ctx* x, const uint64_t* tuples, const int64_t* counts, u
 int pg_clusters_format(pg_ctx* x, char* out, uint64_t cap, uint64_t* n_bytes) {
   return guard([&] {
     if (!x || !n_bytes) throw pg::Error(PG_EINVAL, "pg_clusters_format: bad arguments");
-    if (!x->c.clu_ready) throw pg::Error(PG_EINVAL, "pg_clusters_format: no clustering (call pg_cluster_cc first)");
+    if (!x->c.clu_ready) throw pg::Error(PG_EINVAL, "pg_clusters_format: no clustering (call pg_cluster_cc or pg_cluster_markov first)");
     if (out && cap < x->c.clu_total) throw pg::Error(PG_ERANGE, "pg_clusters_format: buffer too small");
     PG_HIP(hipSetDevice(x->c.device));
     *n_bytes = pg::format_clusters(x->c, out, cap);
@@ -745,7 +788,7 @@ int pg_clusters_format(pg_ctx* x, char* out, uint64_t cap, uint64_t* n_bytes) {
 int pg_clusters_format_fd(pg_ctx* x, int fd, uint64_t* n_bytes) {
   return guard([&] {
     if (!x || !n_bytes || fd < 0) throw pg::Error(PG_EINVAL, "pg_clusters_format_fd: bad arguments");
-    if (!x->c.clu_ready) throw pg::Error(PG_EINVAL, "pg_clusters_format_fd: no clustering (call pg_cluster_cc first)");
+    if (!x->c.clu_ready) throw pg::Error(PG_EINVAL, "pg_clusters_format_fd: no clustering (call pg_cluster_cc or pg_cluster_markov first)");
     PG_HIP(hipSetDevice(x->c.device));
     *n_bytes = pg::format_clusters(x->c, nullptr, 0, fd);
   });

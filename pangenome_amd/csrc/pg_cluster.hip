@@ -20,6 +20,10 @@
 // that its root got a parent.  Every other phase is its own launch on
 // c.stream and reads what earlier launches wrote.
 //
+// pg_cluster.h declares what pg_markov.hip shares with this file: the call's edge list (cc_edges), the node
+// ids (cc_node_ids), the union (cc_union) and the steps from a hooked parent[] to the text and the label
+// table (cc_finish).
+//
 // pg_cluster_sweep (the k_sw_* kernels) asks what the clusterer would form at every weight cut of a
 // list: the same node ids and the same hook, run level by level from the highest threshold down on one
 // parent[] that is flattened in place between levels.
@@ -27,6 +31,7 @@
 #include <climits>
 #include <cstring>
 
+#include "pg_cluster.h"
 #include "pg_internal.h"
 #include "pg_region.h"
 #include "pg_text.h"
@@ -70,37 +75,12 @@ __global__ void k_cc_init(unsigned* __restrict__ parent, uint64_t nu) {
   RG_LOOP(i, nu) parent[i] = (unsigned)i;
 }
 
-__device__ __forceinline__ unsigned cc_load(const unsigned* p) {
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// root of x, with path halving; parent[y] < y for every non-root y, so the walk ends
-__device__ __forceinline__ unsigned cc_find(unsigned* parent, unsigned x) {
-  for (;;) {
-    const unsigned p = cc_load(parent + x);
-    if (p == x) return x;
-    const unsigned g = cc_load(parent + p);
-    if (g != p) __hip_atomic_store(parent + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    x = p;
-  }
-}
-
 __global__ void k_cc_hook(const unsigned* __restrict__ id, const long long* __restrict__ cnt, uint64_t ne,
                           long long min_weight, unsigned* parent) {
   RG_LOOP(e, ne) {
     if (cnt[e] < min_weight) continue;
-    unsigned a = id[2 * e], b = id[2 * e + 1];
-    if (a == b) continue;
-    a = cc_find(parent, a);
-    b = cc_find(parent, b);
-    while (a != b) {
-      if (a < b) { const unsigned t = a; a = b; b = t; }        // the larger root goes under the smaller
-      unsigned expect = a;
-      if (__hip_atomic_compare_exchange_strong(parent + a, &expect, b, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                               __HIP_MEMORY_SCOPE_AGENT))
-        break;
-      a = cc_find(parent, expect);                                // a got a parent meanwhile: go on from it
-      b = cc_find(parent, b);
-    }
+    const unsigned a = id[2 * e], b = id[2 * e + 1];
+    if (a != b) cc_union(parent, a, b);
   }
 }
 
@@ -159,22 +139,7 @@ __global__ void __launch_bounds__(RG_BLOCK) k_sw_hook(const unsigned* __restrict
                                                       ull* hooks) {
   SW_TILES(e, ne, todo) {
     bool won = false;
-    if (todo && cnt[e] >= lo && cnt[e] <= hi) {
-      unsigned a = id[2 * e], b = id[2 * e + 1];
-      a = cc_find(parent, a);
-      b = cc_find(parent, b);
-      while (a != b) {
-        if (a < b) { const unsigned t = a; a = b; b = t; }        // the larger root goes under the smaller
-        unsigned expect = a;
-        if (__hip_atomic_compare_exchange_strong(parent + a, &expect, b, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
-                                                 __HIP_MEMORY_SCOPE_AGENT)) {
-          won = true;
-          break;
-        }
-        a = cc_find(parent, expect);                                // a got a parent meanwhile: go on from it
-        b = cc_find(parent, b);
-      }
-    }
+    if (todo && cnt[e] >= lo && cnt[e] <= hi) won = cc_union(parent, id[2 * e], id[2 * e + 1]);
     const ull m = __ballot(won);
     if (m && (int)(threadIdx.x & 63) == __ffsll(m) - 1) RG_ADD(hooks, (ull)__popcll(m));
   }
@@ -305,21 +270,7 @@ struct MclLine {
   }
 };
 
-// one thread per item of n, up to 8192 blocks
-#define CC_LAUNCH(kern, n, ...) RG_LAUNCH(kern, grid_for((n), RG_BLOCK, 8192), __VA_ARGS__)
-
-// The edge list of a clustering call on the device: the host's tuples and counts uploaded (`up` owns them;
-// -22 in `what`'s name, before any device work, for a node value above 2^32 - 1), or the last edge pass
-// where it lies (h_tuples NULL).  vbits: the bits of the largest value.
-struct CcEdges {
-  DevBuf up;
-  const unsigned long long* tup;
-  const long long* cnt;
-  uint64_t n;
-  int vbits = 32;                              // (the edge pass holds values as 32-bit words)
-};
-static CcEdges cc_edges(Ctx& c, const char* what, const uint64_t* h_tuples, const int64_t* h_counts,
-                        uint64_t n_edges) {
+CcEdges cc_edges(Ctx& c, const char* what, const uint64_t* h_tuples, const int64_t* h_counts, uint64_t n_edges) {
   CcEdges e;
   if (h_tuples) {
     uint64_t maxv = 0;
@@ -342,11 +293,7 @@ static CcEdges cc_edges(Ctx& c, const char* what, const uint64_t* h_tuples, cons
   return e;
 }
 
-// Step a of a clustering call, the node ids: the nn = 2 n_edges > 0 slots sorted by value, then stably by
-// key, positions carried; ids (uint32 [nn]) = every slot's node, numbered by first appearance.  nodes
-// non-null: uint64 [nu] keys, [nu] values of the nodes.  Returns their number nu (-34 in `what`'s name for
-// 2^32 or more); the sort buffers are freed and the stream is idle when it returns.
-static uint64_t cc_node_ids(Ctx& c, const char* what, const CcEdges& e, DevBuf& ids, DevBuf* nodes) {
+uint64_t cc_node_ids(Ctx& c, const char* what, const CcEdges& e, DevBuf& ids, DevBuf* nodes) {
   const unsigned long long* tup = e.tup;
   const uint64_t nn = 2 * e.n;
   uint64_t nu = 0;
@@ -395,24 +342,12 @@ static uint64_t cc_node_ids(Ctx& c, const char* what, const CcEdges& e, DevBuf& 
   return nu;
 }
 
-void cluster_cc(Ctx& c, const uint64_t* h_tuples, const int64_t* h_counts, uint64_t n_edges, int64_t min_weight) {
-  const CcEdges e = cc_edges(c, "pg_cluster_cc", h_tuples, h_counts, n_edges);
-  n_edges = e.n;
-  const long long* cnt = e.cnt;
+void cc_finish(Ctx& c, uint64_t nu, DevBuf& uf, const unsigned long long* nkey, const unsigned long long* nval) {
   c.clu_ready = false;
   c.clu_total = c.n_clusters = c.n_clu_nodes = 0;
-  const uint64_t nn = 2 * n_edges;
-  uint64_t nu = 0, nc = 0;
-  if (nn) {
-    // ---- a. node ids
-    DevBuf ids, nodes;                         // uint32 [nn] ids; uint64 [nu] keys, [nu] values
-    nu = cc_node_ids(c, "pg_cluster_cc", e, ids, &nodes);
-    auto* id = ids.as<unsigned>();
-    auto* nkey = nodes.as<unsigned long long>();
-    auto* nval = nkey + nu;
-    // ---- b-d. union-find over the surviving edges, then the roots and sizes
-    DevBuf uf;                                 // uint32 [nu] x 11
-    uf.reserve(4 * 11 * nu + 16);
+  uint64_t nc = 0;
+  if (nu) {
+    // ---- d. the roots
     auto* parent = uf.as<unsigned>();
     auto* jump_a = parent + nu;
     auto* jump_b = jump_a + nu;
@@ -424,8 +359,6 @@ void cluster_cc(Ctx& c, const uint64_t* h_tuples, const int64_t* h_counts, uint6
     auto* csorted = sm + nu;
     auto* uroot = csorted + nu;
     auto* usize = uroot + nu;
-    CC_LAUNCH(k_cc_init, nu, parent, nu);
-    CC_LAUNCH(k_cc_hook, n_edges, id, cnt, n_edges, (long long)min_weight, parent);
     const unsigned* comp = parent;
     for (int r = 0, rounds = bits_for(nu); r < rounds; ++r) {
       unsigned* out = (r & 1) ? jump_b : jump_a;
@@ -481,6 +414,25 @@ void cluster_cc(Ctx& c, const uint64_t* h_tuples, const int64_t* h_counts, uint6
   c.n_clusters = nc;
   c.n_clu_nodes = nu;
   c.clu_ready = true;
+}
+
+void cluster_cc(Ctx& c, const uint64_t* h_tuples, const int64_t* h_counts, uint64_t n_edges, int64_t min_weight) {
+  const CcEdges e = cc_edges(c, "pg_cluster_cc", h_tuples, h_counts, n_edges);
+  n_edges = e.n;
+  c.clu_ready = false;
+  c.clu_total = c.n_clusters = c.n_clu_nodes = 0;
+  markov_drop(c);
+  DevBuf ids, nodes, uf;                       // uint32 [nn] ids; uint64 [nu] keys, [nu] values; the union-find
+  uint64_t nu = 0;
+  if (n_edges) {
+    // ---- a. node ids
+    nu = cc_node_ids(c, "pg_cluster_cc", e, ids, &nodes);
+    // ---- b, c. union-find over the surviving edges
+    uf.reserve(4 * CC_UF_WORDS * nu + 16);
+    CC_LAUNCH(k_cc_init, nu, uf.as<unsigned>(), nu);
+    CC_LAUNCH(k_cc_hook, n_edges, ids.as<unsigned>(), e.cnt, n_edges, (long long)min_weight, uf.as<unsigned>());
+  }
+  cc_finish(c, nu, uf, nodes.as<unsigned long long>(), nodes.as<unsigned long long>() + nu);
 }
 
 // The cluster curve over thr[0 .. nt) ascending: one union-find that survives from the highest threshold
@@ -559,10 +511,10 @@ void cluster_sweep(Ctx& c, const uint64_t* h_tuples, const int64_t* h_counts, ui
   }
 }
 
-// the `.mcl` text of the last cluster_cc: its size (out null, fd < 0), copied
+// the `.mcl` text of the last cluster_cc or cluster_markov: its size (out null, fd < 0), copied
 // into out, or written to descriptor fd
 uint64_t format_clusters(Ctx& c, char* out, uint64_t cap, int fd) {
-  if (!c.clu_ready) throw Error(-22, "pg_clusters_format: no clustering (call pg_cluster_cc first)");
+  if (!c.clu_ready) throw Error(-22, "pg_clusters_format: no clustering (call pg_cluster_cc or pg_cluster_markov first)");
   return text_out(c, c.clu_text.p, c.clu_total, out, cap, fd, "pg_clusters_format", "pg_clusters_format_fd");
 }
 

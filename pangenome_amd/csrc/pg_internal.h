@@ -296,10 +296,17 @@ struct Ctx {
   uint64_t xyz_total = 0;
   bool xyz_sized = false;
   DevBuf text_buf;                // reusable storage of the `.xyz` and the rows text
-  // ---- built-in clustering (pg_cluster.hip): the `.mcl` text of the last pg_cluster_cc
+  // ---- built-in clustering (pg_cluster.hip, pg_markov.hip): the `.mcl` text of the last pg_cluster_cc or
+  // pg_cluster_markov
   DevBuf clu_text;
   uint64_t clu_total = 0, n_clusters = 0, n_clu_nodes = 0;
   bool clu_ready = false;
+  // the last pg_cluster_markov's final matrix: uint32 [U] col_len, [U x select] rows, [U x select] vals
+  // (released by the next clustering call), and the columns each size class ran, summed over the iterations
+  DevBuf mk_mat;
+  uint64_t mk_nodes = 0, mk_cols_wave = 0, mk_cols_mid = 0, mk_cols_block = 0;
+  uint32_t mk_select = 0;
+  bool mk_ready = false;
   // ---- frequency table (pg_freq.hip): the result of the last pg_freq
   DevBuf fr_tab;                  // [n] label, rows, plus, bases, min, max; [n][W] presence words; uint32 [n] genomes
   DevBuf fr_spec;                 // [2][G + 1]: labels / bases by number of genomes
@@ -458,6 +465,13 @@ uint64_t format_rows_text(Ctx& c, const char* names, const int64_t* name_off, ui
 // text on the device for format_clusters.
 void cluster_cc(Ctx& c, const uint64_t* h_tuples, const int64_t* h_counts, uint64_t n_edges, int64_t min_weight);
 uint64_t format_clusters(Ctx& c, char* out, uint64_t cap, int fd = -1);
+// pg_markov.hip
+// Markov clustering of the same graph (include/pangenome.h has the definition); the result takes cluster_cc's
+// slot and the final matrix stays in c.mk_mat.  markov_drop releases that matrix.
+void cluster_markov(Ctx& c, const uint64_t* h_tuples, const int64_t* h_counts, uint64_t n_edges, int64_t min_weight,
+                    uint32_t inflation2, uint32_t select, uint32_t max_iter, uint32_t* n_iter, uint64_t* chaos);
+void markov_matrix(Ctx& c, uint32_t* col_len, uint32_t* rows, uint32_t* vals);
+void markov_drop(Ctx& c);
 // The cluster curve: row i describes the components cluster_cc would form at min_weight = thr[i] (thr
 // strictly ascending, nt <= SW_MAX_LEVELS, checked by the caller); nt == 0: the node count and the
 // largest count alone.  Every output may be null.  Reads and replaces no result of the context.

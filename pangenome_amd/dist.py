@@ -1135,6 +1135,12 @@ class GpuShard:
         self.ctx.cluster_cc(tuples, counts, int(min_weight))
         return self.ctx.clusters_text()
 
+    def cluster_markov(self, tuples, counts, min_weight, inflation2):
+        """(the `.mcl` bytes, n_iter, chaos) of Markov clustering over a host edge list, the command line's settings"""
+        _, _, n_iter, chaos = self.ctx.cluster_markov(tuples, counts, int(min_weight), int(inflation2), host.MK_SELECT,
+                                                      host.MK_MAX_ITER)
+        return self.ctx.clusters_text(), n_iter, chaos
+
     def cluster_sweep(self, tuples, counts, thresholds):
         """the cluster curve of a host edge list (host.cluster_sweep's dict)"""
         return self.ctx.cluster_sweep(thresholds, tuples, counts)
@@ -1174,6 +1180,12 @@ class GpuShard:
 
 
 # ------------------------------------------------------------------ pipeline
+def _host_markov(tuples, counts, min_weight, inflation2):
+    """GpuShard.cluster_markov for a backend without a device: the specification itself"""
+    r = host.cluster_markov(tuples, counts, min_weight, inflation2, host.MK_SELECT, host.MK_MAX_ITER)
+    return r[0].encode(), r[4], r[5]
+
+
 class DistRun:
     """The CLI stages of entry_point (:2073-2146) over world shards."""
 
@@ -1367,10 +1379,12 @@ class DistRun:
         names = [bytes(self.buf[int(s) + 1:int(s) + int(n)]) for s, n in zip(self.S.hdr_start, self.S.hdr_len)]
         return host.assign_groups(names, host.plan_rows(self.S.seq_len, self.shape, self.buf, int(Ns)), groups)
 
-    def graph(self, Ns, rc1, brkpt="", cluster=True, min_weight=1, groups=None, orders=0):
+    def graph(self, Ns, rc1, brkpt="", cluster=True, min_weight=1, groups=None, orders=0, inflation2=3):
         """seq2graph (:1853-1951) over the shards.  cluster="cc": without a
         `.mcl`, rank 0 writes one with the built-in clusterer (on its device,
         or host.cluster_cc for a backend without one) instead of running mcl;
+        cluster="markov": the same with Markov clustering (the backend's
+        cluster_markov, or host.cluster_markov) at inflation inflation2 / 2;
         min_weight="auto": rank 0 first makes the cluster curve of the merged
         edges (the backend's cluster_sweep, or host.cluster_sweep), writes the
         sweep file and cuts at host.sweep_choice's threshold.
@@ -1434,6 +1448,14 @@ class DistRun:
                     with open(oname + ".mcl.tmp", "wb") as f:   # (renamed when whole: the file is reused if present)
                         f.write(mcl_bytes)
                     os.replace(oname + ".mcl.tmp", oname + ".mcl")
+                elif cluster == "markov":
+                    markov = self.sh.cluster_markov if hasattr(self.sh, "cluster_markov") else _host_markov
+                    mcl_bytes, n_iter, chaos = markov(tuples, counts, int(min_weight), int(inflation2))
+                    with open(oname + ".mcl.tmp", "wb") as f:
+                        f.write(mcl_bytes)
+                    os.replace(oname + ".mcl.tmp", oname + ".mcl")
+                    if host.markov_note(n_iter, chaos):
+                        self.say(host.markov_note(n_iter, chaos))
                 else:
                     self.out.flush()
                     os.system("mcl %s --abc -I 1.5 -te 8 -o %s.mcl -q x -V all" % (oname, oname))
@@ -1507,7 +1529,7 @@ def entry_point(argv, out=None, shard_factory=None, device=None, dev_index: int 
     group; rank 0 prints.  `shard_factory(k)` makes the rank's backend
     (default: GpuShard on dev_index)."""
     import torch.distributed as dist
-    from .kmer import compare_orders_arg, manual_print, parse_args, weight_arg
+    from .kmer import cluster_args, compare_orders_arg, manual_print, parse_args
     out = out or sys.stdout
     args = parse_args(argv)
     qry, kmer, Ns = args["-i"], int(args["-k"]), host.eval_number(args["-n"])
@@ -1515,11 +1537,12 @@ def entry_point(argv, out=None, shard_factory=None, device=None, dev_index: int 
     n_orders = compare_orders_arg(args)
     # -l (the region graph) is single process only: merging the ranks' link tables needs per-(link, genome) pairs;
     # so is -s (the region sequences): a label's representative may lie in another rank's records
-    if not qry or args["-a"] not in ("mcl", "cc") or n_orders is None or args["-l"] != "0" or args["-s"] != "0":
+    bad = not qry or n_orders is None or args["-l"] != "0" or args["-s"] != "0"
+    clu = None if bad else cluster_args(args)
+    if clu is None:
         if dist.get_rank() == 0:
             manual_print(out)
         raise SystemExit()
-    clu = dict(cluster="cc", min_weight=weight_arg(args)) if args["-a"] == "cc" else {}
     if args["-g"]:
         clu["groups"] = args["-g"]
     if n_orders:

@@ -321,6 +321,155 @@ def cluster_cc(tuples: np.ndarray, counts: np.ndarray, min_weight: int = 1):
     return text, uniq[file_order, 0].view(np.int64), uniq[file_order, 1].view(np.int64), line
 
 
+MK_ONE = 1 << 31                 # pg_cluster_markov's fixed point: 1.0
+MK_CUT = MK_ONE // 10000         # entries below it are pruned (a column's first entry stays)
+MK_STOP = MK_ONE // 1000         # the iteration stops at this chaos
+MK_SELECT, MK_MAX_ITER = 64, 200 # what the command line runs with
+
+
+def markov_note(n_iter, chaos):
+    """the line -a markov prints before the rows when the iteration cap was reached, else None"""
+    if n_iter >= MK_MAX_ITER and chaos > MK_STOP:
+        return "# -a markov: not converged after %d iterations (chaos %.6f)" % (MK_MAX_ITER, chaos / MK_ONE)
+    return None
+
+
+def _mk_isqrt(x):
+    """floor(sqrt(x)) of a uint64 array, exact: the double root, then fixed down and up."""
+    one = np.uint64(1)
+    s = np.sqrt(x.astype(np.float64)).astype(np.uint64)
+    while True:
+        m = s * s > x
+        if not m.any():
+            break
+        s[m] -= one
+    while True:
+        m = (s + one) * (s + one) <= x
+        if not m.any():
+            break
+        s[m] += one
+    return s
+
+
+def _mk_prune(col, row, f, U, select):
+    """prune() of every column at once.  col, row (int64) and f (uint64, positive) list the candidates in
+    any order, every column at least one; returns (col, row, value) by (col, row) and the columns' starts."""
+    o = np.lexsort((row, col))
+    col, row, f = col[o], row[o], f[o]
+    start = np.searchsorted(col, np.arange(U))
+    n = (f << np.uint64(31)) // np.add.reduceat(f, start)[col]
+    o = np.lexsort((row, np.uint64(1 << 32) - n, col))       # n descending, then row ascending
+    col, row, n = col[o], row[o], n[o]
+    rank = np.arange(col.shape[0]) - start[col]
+    keep = (rank == 0) | ((n >= np.uint64(MK_CUT)) & (rank < select))
+    col, row, n = col[keep], row[keep], n[keep]
+    start = np.searchsorted(col, np.arange(U))
+    v = (n << np.uint64(31)) // np.add.reduceat(n, start)[col]
+    o = np.lexsort((row, col))
+    return col[o], row[o], v[o], start
+
+
+def _mk_chaos(v, start):
+    if not v.shape[0]:
+        return 0
+    return int((np.maximum.reduceat(v, start) - (np.add.reduceat(v * v, start) >> np.uint64(31))).max())
+
+
+def _mk_step(col, row, val, start, U, inflation2, select):
+    """one iteration: expansion, scaling, inflation, prune"""
+    u31 = np.uint64(31)
+    length = np.diff(np.append(start, col.shape[0]))
+    reps = length[row]                                       # entry (k = row, j = col) meets column k whole
+    e_of = np.repeat(np.arange(col.shape[0]), reps)
+    src = start[row[e_of]] + (np.arange(e_of.shape[0]) - np.repeat(np.cumsum(reps) - reps, reps))
+    cc, cr, prod = col[e_of], row[src], val[src] * val[e_of]
+    o = np.lexsort((cr, cc))
+    cc, cr, prod = cc[o], cr[o], prod[o]
+    head = np.flatnonzero(np.append(True, (cc[1:] != cc[:-1]) | (cr[1:] != cr[:-1])))
+    cc, cr, e = cc[head], cr[head], np.add.reduceat(prod, head) >> u31
+    cstart = np.searchsorted(cc, np.arange(U))
+    x = (e << u31) // np.maximum.reduceat(e, cstart)[cc]
+    y = np.full(x.shape[0], MK_ONE, np.uint64)
+    for _ in range(inflation2 // 2):
+        y = (y * x) >> u31
+    if inflation2 & 1:
+        y = (y * _mk_isqrt(x << u31)) >> u31
+    live = y > 0
+    return _mk_prune(cc[live], cr[live], y[live], U, select)
+
+
+def cluster_markov(tuples, counts, min_weight: int = 1, inflation2: int = 3, select: int = 64, max_iter: int = 200):
+    """Markov clustering's specification (pg_cluster_markov computes the same
+    on the device, bit for bit): the definition of include/pangenome.h in
+    unsigned integers, 1.0 = MK_ONE.  Nodes as cluster_cc; w(i, j) = the summed
+    counts >= min_weight of the edges between i != j, a loop of the column's
+    largest weight (1 without an edge); columns pruned to `select` entries;
+    per iteration the expansion M x M, the scaling to the column's largest,
+    the inflation by inflation2 / 2 and the prune, until the chaos is at most
+    MK_STOP or max_iter iterations ran.  Clusters: the components of the last
+    matrix's stored entries, ordered and written as cluster_cc does.  Returns
+    cluster_cc's four values, then n_iter, chaos and the matrix (col_len
+    uint32 [U], rows and vals uint32 [U, select], zero beyond a column's
+    length).  Also the fallback of a shard backend without a device."""
+    min_weight, inflation2, select, max_iter = int(min_weight), int(inflation2), int(select), int(max_iter)
+    if min_weight < 1:
+        raise ValueError("cluster_markov: min_weight below 1")
+    if not 3 <= inflation2 <= 40:
+        raise ValueError("cluster_markov: inflation2 outside [3, 40]")
+    if not 1 <= select <= 64:
+        raise ValueError("cluster_markov: select outside [1, 64]")
+    if not 0 <= max_iter <= 10000:
+        raise ValueError("cluster_markov: max_iter outside [0, 10000]")
+    t = np.ascontiguousarray(tuples, dtype=np.uint64).reshape(-1, 4)
+    cnt = np.ascontiguousarray(counts, dtype=np.int64)
+    if cnt.shape[0] != t.shape[0]:
+        raise ValueError("cluster_markov: %d tuples, %d counts" % (t.shape[0], cnt.shape[0]))
+    if t.shape[0] == 0:
+        z = np.zeros(0, np.int64)
+        return "", z, z.copy(), z.copy(), 0, 0, (np.zeros(0, np.uint32), np.zeros((0, select), np.uint32),
+                                                 np.zeros((0, select), np.uint32))
+    ids, uniq = _node_ids(t)
+    U = uniq.shape[0]
+    # ---- the weights: undirected pairs summed, then both directions and the loops
+    keep = (cnt >= min_weight) & (ids[:, 0] != ids[:, 1])
+    a, b = ids[keep].min(axis=1), ids[keep].max(axis=1)
+    o = np.lexsort((b, a))
+    a, b, w = a[o], b[o], cnt[keep][o].astype(object)        # (Python integers: the sum has no limit here)
+    head = np.flatnonzero(np.append(True, (a[1:] != a[:-1]) | (b[1:] != b[:-1]))) if a.shape[0] else np.zeros(0, np.int64)
+    w = np.add.reduceat(w, head) if a.shape[0] else w
+    if any(int(x) >= 1 << 32 for x in w):
+        raise OverflowError("cluster_markov: a summed weight of 2^32 or more")
+    a, b, w = a[head], b[head], w.astype(np.uint64)
+    loop = np.ones(U, np.uint64)
+    big = np.zeros(U, np.uint64)
+    np.maximum.at(big, a, w)
+    np.maximum.at(big, b, w)
+    loop = np.maximum(loop, big)
+    col = np.concatenate([a, b, np.arange(U)]).astype(np.int64)
+    row = np.concatenate([b, a, np.arange(U)]).astype(np.int64)
+    col, row, val, start = _mk_prune(col, row, np.concatenate([w, w, loop]), U, select)
+    chaos, n_iter = _mk_chaos(val, start), 0
+    while n_iter < max_iter:
+        col, row, val, start = _mk_step(col, row, val, start, U, inflation2, select)
+        chaos, n_iter = _mk_chaos(val, start), n_iter + 1
+        if chaos <= MK_STOP:
+            break
+    col_len = np.diff(np.append(start, col.shape[0])).astype(np.uint32)
+    rows = np.zeros((U, select), np.uint32)
+    vals = np.zeros((U, select), np.uint32)
+    at = np.arange(col.shape[0]) - start[col]
+    rows[col, at] = row
+    vals[col, at] = val
+    # ---- the clusters: components of the stored entries, cluster_cc's order and text
+    edges = np.zeros((col.shape[0], 4), np.uint64)
+    edges[:, 0:2] = uniq[col]
+    edges[:, 2:4] = uniq[row]
+    # (cluster_cc numbers nodes by first appearance: lead with every node in id order, as loops)
+    lead = np.concatenate([uniq, uniq], axis=1)
+    text, k, v, line = cluster_cc(np.concatenate([lead, edges]), np.ones(U + col.shape[0], np.int64), 1)
+    return text, k, v, line, n_iter, chaos, (col_len, rows, vals)
+
+
 SWEEP_MAX_LEVELS = 4096          # pg_cluster_sweep's limit
 
 

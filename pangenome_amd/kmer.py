@@ -257,14 +257,19 @@ def rdbg_edges(g: DeviceGraph, Ns, chunk, rc, brkpt="", keep_on_device=False):
 
 def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_dict=None, saved=None,
               hashfunc=None, jit=True, chunk=2 ** 33, rc=False, cluster=True, out=None, min_weight=1, groups=None,
-              orders=0, links=False, seqs=False):
+              orders=0, links=False, seqs=False, inflation2=3):
     """:1853-1951: edge weights -> `<qry>_rdbg_weight.xyz` -> mcl (or reuse)
     -> label dictionary -> print the region rows.  The edges, the label
     table, the rows and both texts are made on the device; the host writes
     the files and runs (or reuses) mcl.  cluster="cc": instead of running
     mcl, the built-in clusterer (pg_cluster_cc: edges lighter than min_weight
     dropped, connected components of the rest) writes the `.mcl`; an existing
-    `.mcl` is reused either way.  min_weight="auto" (with cluster="cc"): the
+    `.mcl` is reused either way.  cluster="markov": the built-in Markov
+    clustering (pg_cluster_markov on the device edges where they lie: edges
+    lighter than min_weight dropped, inflation inflation2 / 2, 64 entries per
+    column, at most 200 iterations) writes the `.mcl` the same way; a run
+    that reaches the cap prints one `# -a markov: not converged` line before
+    the rows.  min_weight="auto" (with cluster="cc"): the
     cluster curve of the `.xyz` over host.sweep_thresholds is made first
     (pg_cluster_sweep, on the device edges where they lie), written as
     `<qry>_rdbg_weight.xyz.sweep.tsv`, and host.sweep_choice's threshold is
@@ -309,6 +314,16 @@ def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_
             with open(oname + ".mcl.tmp", "wb") as f:           # (renamed when whole: the file is reused if present)
                 g.ctx.clusters_write(f.fileno())
             os.replace(oname + ".mcl.tmp", oname + ".mcl")
+            clustered = True
+        elif cluster == "markov":
+            _, _, n_iter, chaos = g.ctx.cluster_markov(None if res is None else res[0], None if res is None else res[1],
+                                                       int(min_weight), int(inflation2), host.MK_SELECT, host.MK_MAX_ITER)
+            with open(oname + ".mcl.tmp", "wb") as f:
+                g.ctx.clusters_write(f.fileno())
+            os.replace(oname + ".mcl.tmp", oname + ".mcl")
+            note = host.markov_note(n_iter, chaos)
+            if note:
+                print(note, file=out)
             clustered = True
         else:
             out.flush()
@@ -445,6 +460,7 @@ def manual_print(out=None):
                  "  -i: query sequences in fasta format", "  -k: kmer length",
                  "  -d: the de bruijn graph", "  -r: break point of de bruijn graph",
                  "  -D: the reduced de bruijn graph", "  -R: break point of reduced de bruijn graph",
+                 "  -I: with -a markov, the inflation. a multiple of 0.5 from 1.5 to 20. default 1.5",
                  "  -n: length of query sequences for pan-genomic analysis",
                  "  -s: with -g, one representative sequence per region. 0 (off) or 1; single process only. writes",
                  "      <in>_fr_regions.fa, _fr_regions.tsv and, with -l 1, _fr_graph_seq.gfa (GFA 1 with sequences)",
@@ -455,16 +471,17 @@ def manual_print(out=None):
                  "  -l: with -g, the graph of the regions along the genomes. 0 (off) or 1; single process only. writes",
                  "      <in>_fr_links.tsv, _fr_nodes.tsv, _fr_graph.gfa (GFA 1, the genomes as paths), _fr_graph.npz",
                  "  -c: complementary reverse sequence. 00,01,10,11",
-                 "  -a: clustering of the rdBG. mcl (run or reuse mcl) or cc (built-in connected components)",
-                 "  -w: with -a cc, drop edges lighter than this weight. default 1. auto: the weight with the most clusters of "
-                 "2+ nodes, from the cluster curve written to <in>_rdbg_weight.xyz.sweep.tsv"):
+                 "  -a: clustering of the rdBG. mcl (run or reuse mcl), cc (built-in connected components) or markov "
+                 "(built-in Markov clustering)",
+                 "  -w: with -a cc or markov, drop edges lighter than this weight. default 1. auto: the weight with the most clusters of "
+                 "2+ nodes, from the cluster curve written to <in>_rdbg_weight.xyz.sweep.tsv (auto: -a cc only)"):
         print(line, file=out)
 
 
 def parse_args(argv):
     """:1983-1997 — same flag handling, including `-k27` and skipped unknowns."""
     args = {"-i": "", "-k": "50", "-n": "2**63", "-r": "", "-d": "", "-R": "", "-D": "", "-c": "2", "-a": "mcl",
-            "-w": "1", "-g": "", "-p": "0", "-l": "0", "-s": "0"}
+            "-w": "1", "-g": "", "-p": "0", "-l": "0", "-s": "0", "-I": "1.5"}
     N = len(argv)
     for i in range(1, N):
         k = argv[i]
@@ -479,6 +496,30 @@ def weight_arg(args):
     """-w's value with -a cc: "auto" or an integer (anything else raises
     ValueError, as int() does)."""
     return "auto" if args["-w"] == "auto" else int(args["-w"])
+
+
+def inflation_arg(args):
+    """-I's value as pg_cluster_markov's inflation2 = 2 r: r a decimal multiple
+    of 0.5 in [1.5, 20]; None for anything else."""
+    import re
+    m = re.fullmatch(r"(\d+)(?:\.([05])0*)?", args["-I"])
+    if not m:
+        return None
+    i2 = 2 * int(m.group(1)) + (m.group(2) == "5")
+    return i2 if 3 <= i2 <= 40 else None
+
+
+def cluster_args(args):
+    """seq2graph's clustering keywords from -a, -w and -I, or None for a
+    combination that is refused (-I is read with -a markov alone)."""
+    if args["-a"] == "cc":
+        return dict(cluster="cc", min_weight=weight_arg(args))
+    if args["-a"] == "markov":
+        i2 = inflation_arg(args)
+        if i2 is None or args["-w"] == "auto":
+            return None
+        return dict(cluster="markov", min_weight=int(args["-w"]), inflation2=i2)
+    return {} if args["-a"] == "mcl" else None
 
 
 def compare_orders_arg(args):
@@ -513,10 +554,11 @@ def entry_point(argv, out=None, device=0):
     qry, kmer, Ns = args["-i"], int(args["-k"]), host.eval_number(args["-n"])
     bkt, dbs, rbk, rc, rdb = args["-r"], args["-d"], args["-R"], int(args["-c"]), args["-D"]
     n_orders, links, seqs = compare_orders_arg(args), links_arg(args), seqs_arg(args)
-    if not qry or args["-a"] not in ("mcl", "cc") or n_orders is None or links is None or seqs is None:
+    bad = not qry or n_orders is None or links is None or seqs is None
+    clu = None if bad else cluster_args(args)
+    if clu is None:
         manual_print(out)
         raise SystemExit()
-    clu = dict(cluster="cc", min_weight=weight_arg(args)) if args["-a"] == "cc" else {}
     grp = args["-g"]
     if grp:
         clu["groups"] = grp
