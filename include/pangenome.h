@@ -671,6 +671,73 @@ int pg_region_gfa_seq(pg_ctx* ctx, const char* names, const int64_t* name_off, u
 int pg_region_gfa_seq_fd(pg_ctx* ctx, const char* names, const int64_t* name_off, uint64_t n_names, int fd,
                          uint64_t* n_bytes);
 
+/* ---- variable sites: where the genomes differ - the simple bubbles of the
+ *      region graph.  A site is a pair of flanking labels (a, c) that the
+ *      genomes join in two or more ways: directly, or through one region x.
+ *      Integer only; the result depends on the input alone, whatever the
+ *      schedule.
+ * Input: exactly pg_region_graph's - rows, rec_group, the rule for a used
+ * row, the run, and the count of the others in *n_skipped (every count
+ * pointer may be NULL).
+ * Record: two consecutive rows of a run with labels (a, c) give a direct
+ * record - site (a, c), via = -1, length 0; three consecutive rows with labels
+ * (a, x, c) give a via record - site (a, c), via = x, length |end - start| of
+ * the middle row (unsigned 64-bit, as pg_freq).  Walk order, as the links: no
+ * orientation is inferred, the reverse walk's labels are other labels and its
+ * bubbles other sites.  a == c, x == a and x == c are legal.  The genome of a
+ * record is rec_group[record].  *n_records_emitted: the records, direct and
+ * via.
+ * Allele of a flank pair: a distinct via.  Site: a flank pair with two
+ * alleles or more; a pair with one allele - the conserved chain - is dropped.
+ * LIMIT: only bubbles with at most one region inside are found.  An insertion
+ * of two regions against a direct join is a pair (a, c) with the direct
+ * allele alone and is not reported, nor is it pieced together from shorter
+ * sites.
+ * Alleles table, by (a, c, via) ascending - the direct allele first in its
+ * site: site, the index of its site; via; count, its records; n_genomes, the
+ * distinct genomes among them; min_len and max_len over their lengths; the
+ * presence set, W = ceil(n_groups / 64) uint64 words with genome g at bit
+ * g % 64 of word g / 64 (as pg_freq_export).
+ * Sites table, by (a, c) ascending: from = a, to = c; n_alleles; first, the
+ * index of its first allele; count, the sum over its alleles; n_genomes, the
+ * popcount of the OR of their presence sets.
+ * Per genome (n_groups entries): sites, the sites where it carries any
+ * allele; alleles, the allele entries with its bit set; private, the allele
+ * entries whose only genome it is.
+ * PG_EINVAL, before any device work: pg_region_graph's whole list.  L = 1 +
+ * the largest used label > 2^31 is PG_ERANGE (found by a device reduction
+ * before anything is allocated).  Nothing is dense in the label: the call
+ * takes device memory by the rows and the records (a run of r rows gives
+ * 2 r - 3 of them) - 9 bytes per row, 37 per used row for the steps, 64 per
+ * record while they are sorted, then 49 per record and at most 58 more per
+ * allele of any pair for the flags, their scans and the heads - and the tables
+ * 44 + 8 W bytes per allele and 40 + 8 W per site.  An allocation failure is PG_ENOMEM.  In every refusal
+ * the previous result stays: the new one is built aside and swapped in last.
+ * The result stays until the next successful pg_region_sites; pg_freq,
+ * pg_freq_compare, pg_region_graph and pg_region_seqs neither read nor drop
+ * it, nor it theirs. */
+int pg_region_sites(pg_ctx* ctx, const int64_t* rows5, uint64_t n_rows, const int32_t* rec_group,
+                    uint64_t n_records, uint32_t n_groups, uint64_t* n_sites, uint64_t* n_alleles,
+                    uint64_t* n_records_emitted, uint64_t* n_skipped);
+/* The three tables of the last pg_region_sites; any output pointer may be
+ * NULL; cap (entries; bits takes W words per entry) below the table's size is
+ * PG_ERANGE.  These and the two text calls below: PG_EINVAL before any
+ * pg_region_sites. */
+int pg_region_sites_table(pg_ctx* ctx, int64_t* from, int64_t* to, uint32_t* n_alleles, uint64_t* first,
+                          uint64_t* count, uint32_t* n_genomes, uint64_t cap);
+int pg_region_sites_alleles(pg_ctx* ctx, uint64_t* site, int64_t* via, uint64_t* count, uint32_t* n_genomes,
+                            uint64_t* min_len, uint64_t* max_len, uint64_t* bits, uint64_t cap);
+int pg_region_sites_groups(pg_ctx* ctx, uint64_t* sites, uint64_t* alleles, uint64_t* private_alleles,
+                           uint64_t cap);                                    /* cap >= n_groups */
+/* The alleles table's text, formatted on the device and kept there like
+ * pg_region_links_format's: the header
+ * "#from\tto\tvia\tcount\tgenomes\tmin\tmax\n", then one line of decimals per
+ * allele in table order, `*` for the direct allele's via (no sites: the
+ * header alone).  out, cap, n_bytes and the _fd form: as
+ * pg_region_links_format and pg_region_links_format_fd. */
+int pg_region_sites_format(pg_ctx* ctx, char* out, uint64_t cap, uint64_t* n_bytes);
+int pg_region_sites_format_fd(pg_ctx* ctx, int fd, uint64_t* n_bytes);
+
 /* ---- text output (host only; no context).  The reference formats these in
  *      Python loops (kmer_numba.py:1893-1904, :1946-1949).
  * pg_format_xyz: "%d_%d\t%d_%d\t%d\n" per edge (tuples as unsigned).

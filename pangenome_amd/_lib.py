@@ -131,6 +131,12 @@ SIGNATURES = {
     "pg_region_fasta_fd": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, _U64P]),
     "pg_region_gfa_seq": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint64, _U64P]),
     "pg_region_gfa_seq_fd": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, _U64P]),
+    "pg_region_sites": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, C.c_uint32, _U64P, _U64P, _U64P, _U64P]),
+    "pg_region_sites_table": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_uint64]),
+    "pg_region_sites_alleles": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_uint64]),
+    "pg_region_sites_groups": (C.c_int, [_P, _P, _P, _P, C.c_uint64]),
+    "pg_region_sites_format": (C.c_int, [_P, _P, C.c_uint64, _U64P]),
+    "pg_region_sites_format_fd": (C.c_int, [_P, C.c_int, _U64P]),
     "pg_rows_format": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint64, _U64P]),
     "pg_rows_format_fd": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, _U64P]),
     "pg_get_stats": (C.c_int, [_P, _SP]),
@@ -919,6 +925,61 @@ class Context:
         """region_gfa_seq_text(names) written straight to descriptor fd at its
         position (pg_region_gfa_seq_fd); flush any buffered writer on fd first."""
         return _write(self.h, self.lib.pg_region_gfa_seq_fd, "pg_region_gfa_seq_fd", fd, *_names_args(names))
+
+    # ---------------------------------------------------- variable sites
+    def region_sites(self, rec_group, n_groups: int, rows=None):
+        """The variable sites (pg_region_sites) of the last row pass where it
+        lies on the device (rows None) or of host rows [n, 5]; rec_group as
+        region_graph() takes it.  Returns (n_sites, n_alleles, n_records,
+        n_skipped); the result stays on the device (region_sites_table /
+        region_sites_alleles / region_sites_groups / region_sites_text and
+        region_sites_write)."""
+        r5, n_rows, grp, n_records = _row_args(rec_group, rows)
+        ns, na, nr, nk = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        check(self.lib.pg_region_sites(self.h, ptr(r5), n_rows, ptr(grp), n_records, int(n_groups),
+                                       C.byref(ns), C.byref(na), C.byref(nr), C.byref(nk)), "pg_region_sites")
+        self.n_sites = (ns.value, na.value, int(n_groups))
+        return ns.value, na.value, nr.value, nk.value
+
+    def region_sites_table(self) -> dict:
+        """The sites of the last region_sites() by (from, to) ascending:
+        site_from, site_to, site_alleles, site_first, site_count,
+        site_genomes (pg_region_sites_table)."""
+        n = getattr(self, "n_sites", (0, 0, 0))[0]
+        t = {"site_from": np.empty(n, np.int64), "site_to": np.empty(n, np.int64),
+             "site_alleles": np.empty(n, np.uint32), "site_first": np.empty(n, np.uint64),
+             "site_count": np.empty(n, np.uint64), "site_genomes": np.empty(n, np.uint32)}
+        check(self.lib.pg_region_sites_table(self.h, *[ptr(a) for a in t.values()], n), "pg_region_sites_table")
+        return t
+
+    def region_sites_alleles(self) -> dict:
+        """The alleles by (from, to, via) ascending: allele_site, allele_via
+        (-1: the direct join), allele_count, allele_genomes, allele_min,
+        allele_max and bits, uint64 [n, W] (pg_region_sites_alleles)."""
+        _, n, G = getattr(self, "n_sites", (0, 0, 0))
+        t = {"allele_site": np.empty(n, np.uint64), "allele_via": np.empty(n, np.int64),
+             "allele_count": np.empty(n, np.uint64), "allele_genomes": np.empty(n, np.uint32),
+             "allele_min": np.empty(n, np.uint64), "allele_max": np.empty(n, np.uint64),
+             "bits": np.empty((n, (G + 63) // 64), np.uint64)}
+        check(self.lib.pg_region_sites_alleles(self.h, *[ptr(a) for a in t.values()], n), "pg_region_sites_alleles")
+        return t
+
+    def region_sites_groups(self) -> dict:
+        """Per genome: genome_sites, genome_alleles, genome_private
+        (pg_region_sites_groups)."""
+        G = getattr(self, "n_sites", (0, 0, 0))[2]
+        t = {k: np.empty(G, np.uint64) for k in ("genome_sites", "genome_alleles", "genome_private")}
+        check(self.lib.pg_region_sites_groups(self.h, *[ptr(a) for a in t.values()], G), "pg_region_sites_groups")
+        return t
+
+    def region_sites_text(self) -> bytes:
+        """The alleles table's text, formatted on the device (pg_region_sites_format)."""
+        return _text(self.h, self.lib.pg_region_sites_format, "pg_region_sites_format")
+
+    def region_sites_write(self, fd: int) -> int:
+        """region_sites_text() written straight to descriptor fd at its
+        position (pg_region_sites_format_fd); flush any buffered writer on fd first."""
+        return _write(self.h, self.lib.pg_region_sites_format_fd, "pg_region_sites_format_fd", fd)
 
     def rows_export(self, n: int):
         """The [n, 5] rows of the last rows_count() (pg_rows_export)."""

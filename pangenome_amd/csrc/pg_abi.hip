@@ -1012,6 +1012,59 @@ int pg_region_gfa_seq_fd(pg_ctx* x, const char* names, const int64_t* name_off, 
   });
 }
 
+int pg_region_sites(pg_ctx* x, const int64_t* rows5, uint64_t n_rows, const int32_t* rec_group, uint64_t n_records,
+                    uint32_t n_groups, uint64_t* n_sites, uint64_t* n_alleles, uint64_t* n_records_emitted,
+                    uint64_t* n_skipped) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_region_sites: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::region_sites(x->c, rows5, n_rows, rec_group, n_records, n_groups, n_sites, n_alleles, n_records_emitted,
+                     n_skipped);
+  });
+}
+
+int pg_region_sites_table(pg_ctx* x, int64_t* from, int64_t* to, uint32_t* n_alleles, uint64_t* first,
+                          uint64_t* count, uint32_t* n_genomes, uint64_t cap) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_region_sites_table: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::region_sites_table(x->c, from, to, n_alleles, first, count, n_genomes, cap);
+  });
+}
+
+int pg_region_sites_alleles(pg_ctx* x, uint64_t* site, int64_t* via, uint64_t* count, uint32_t* n_genomes,
+                            uint64_t* min_len, uint64_t* max_len, uint64_t* bits, uint64_t cap) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_region_sites_alleles: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::region_sites_alleles(x->c, site, via, count, n_genomes, min_len, max_len, bits, cap);
+  });
+}
+
+int pg_region_sites_groups(pg_ctx* x, uint64_t* sites, uint64_t* alleles, uint64_t* private_alleles, uint64_t cap) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_region_sites_groups: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::region_sites_groups(x->c, sites, alleles, private_alleles, cap);
+  });
+}
+
+int pg_region_sites_format(pg_ctx* x, char* out, uint64_t cap, uint64_t* n_bytes) {
+  return guard([&] {
+    if (!x || !n_bytes) throw pg::Error(PG_EINVAL, "pg_region_sites_format: bad arguments");
+    PG_HIP(hipSetDevice(x->c.device));
+    *n_bytes = pg::format_region_sites(x->c, out, cap);
+  });
+}
+
+int pg_region_sites_format_fd(pg_ctx* x, int fd, uint64_t* n_bytes) {
+  return guard([&] {
+    if (!x || !n_bytes || fd < 0) throw pg::Error(PG_EINVAL, "pg_region_sites_format_fd: bad arguments");
+    PG_HIP(hipSetDevice(x->c.device));
+    *n_bytes = pg::format_region_sites(x->c, nullptr, 0, fd);
+  });
+}
+
 int pg_rows_format(pg_ctx* x, const char* names, const int64_t* name_off, uint64_t n_names, char* out, uint64_t cap,
                    uint64_t* n_bytes) {
   return guard([&] {

@@ -341,6 +341,15 @@ struct Ctx {
   Timer t_rs;                     // the decoder kernel of the last pg_region_seqs (HIP events on `stream`)
   double ms_rs_decode = 0;
   uint64_t rs_chunks = 0;         // its 16-letter chunks
+  // ---- variable sites (pg_sites.hip): the result of the last pg_region_sites
+  DevBuf vs_sites;                // [n] from, to, first, count; uint32 [n] alleles, genomes
+  DevBuf vs_alleles;              // [n] site, via, count, min, max; uint32 [n] genomes
+  DevBuf vs_bits;                 // [alleles][W] presence words
+  DevBuf vs_grp;                  // [3][G]: sites, alleles, private per genome
+  DevBuf vs_text;                 // the alleles' text
+  uint64_t vs_ns = 0, vs_na = 0, vs_total = 0;
+  uint32_t vs_groups = 0, vs_words = 0;
+  bool vs_ready = false;
 
   // ---- npz persistence (pg_persist.hip)
   DevBuf preload;                 // staged PreEnt pairs, OR-merged by every build
@@ -546,6 +555,7 @@ DevNames names_upload(Ctx& c, const char* what, const char* names, const int64_t
 #define NEED_COMPARE "no comparison (call pg_freq_compare first)"
 #define NEED_GRAPH "no region graph (call pg_region_graph first)"
 #define NEED_SEQS "no region sequences (call pg_region_seqs first)"
+#define NEED_SITES "no variable sites (call pg_region_sites first)"
 inline void need(bool ready, const char* what, const char* hint) {
   if (!ready) throw Error(-22, std::string(what) + ": " + hint);
 }
@@ -585,6 +595,20 @@ uint64_t format_region_fasta(Ctx& c, const char* names, const int64_t* name_off,
 void region_seqs_match(Ctx& c, const char* what);
 const unsigned long long* region_seqs_len(Ctx& c);
 void region_seqs_copy(Ctx& c, const unsigned long long* d_dst_off, char* d_dst);
+
+// pg_sites.hip
+// The variable sites of rows (h_rows5 NULL: the last row pass) grouped by
+// rec_group: the flank pairs (a, c) that two or more alleles join; replaces the
+// context's previous sites only when it succeeds.
+void region_sites(Ctx& c, const int64_t* h_rows5, uint64_t n_rows, const int32_t* rec_group, uint64_t n_records,
+                  uint32_t n_groups, uint64_t* n_sites, uint64_t* n_alleles, uint64_t* n_records_emitted,
+                  uint64_t* n_skipped);
+void region_sites_table(Ctx& c, int64_t* from, int64_t* to, uint32_t* n_alleles, uint64_t* first, uint64_t* count,
+                        uint32_t* n_genomes, uint64_t cap);
+void region_sites_alleles(Ctx& c, uint64_t* site, int64_t* via, uint64_t* count, uint32_t* n_genomes,
+                          uint64_t* min_len, uint64_t* max_len, uint64_t* bits, uint64_t cap);
+void region_sites_groups(Ctx& c, uint64_t* sites, uint64_t* alleles, uint64_t* private_, uint64_t cap);
+uint64_t format_region_sites(Ctx& c, char* out, uint64_t cap, int fd = -1);
 
 // helpers
 inline uint64_t next_pow2(uint64_t x) {

@@ -1,9 +1,11 @@
 // pg_region.h — the device side of what the passes over the region rows share
 // (pg_freq.hip, the frequency table; pg_region.hip, the region graph;
-// pg_regionseq.hip, the region sequences): the row and the rule for a used one
-// (RgRow, rs_used), a tile of rows through LDS with or without the row before
-// it (rg_load_tile), the wave reductions, the lanes of a wave grouped by label
-// (rg_by_label) and the node table of the graph.  The
+// pg_regionseq.hip, the region sequences; pg_sites.hip, the variable sites):
+// the row and the rule for a used one (RgRow, rs_used), the flag byte
+// k_row_scan gives a row and the scan of one of its bits (scan_bit), a tile of
+// rows through LDS with or without the row before it (rg_load_tile), the wave
+// reductions, the lanes of a wave grouped by label (rg_by_label) and the node
+// table of the graph.  The
 // loop, launch and atomic macros are pg_prim.h's; the host side (row_input,
 // row_scan, labels_seen, text_out, names_upload) is declared in pg_internal.h
 // and lives at the top of pg_region.hip.
@@ -14,6 +16,24 @@
 namespace pg {
 
 #define RG_AGG_MIN 4               // lanes of a wave sharing a label before one lane issues for them
+#define RG_USED 1u                 // flag byte of a row (k_row_scan): it is used
+#define RG_HEAD 2u                 //                                  it starts a run
+
+// off[0 .. n]: the flag bytes with `bit` set before each position (f[n] must be 0); returns off[n]
+struct RgBit {
+  uint32_t bit;
+  __host__ __device__ ull operator()(uint8_t f) const { return (f & bit) ? 1ull : 0ull; }
+};
+[[maybe_unused]] static uint64_t scan_bit(Ctx& c, const uint8_t* f, uint32_t bit, ull* off, uint64_t n) {
+  with_temp(c, [&](void* tmp, size_t& bytes) {
+    return rocprim::exclusive_scan(tmp, bytes, rocprim::make_transform_iterator(f, RgBit{bit}), off, 0ull,
+                                   (size_t)n + 1, rocprim::plus<ull>(), c.stream);
+  });
+  ull h = 0;
+  PG_HIP(hipMemcpyAsync(&h, off + n, 8, hipMemcpyDeviceToHost, c.stream));
+  c.sync();
+  return h;
+}
 
 struct RgRow {
   long long rec, start, end, strand, label;

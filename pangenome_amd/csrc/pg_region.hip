@@ -53,9 +53,7 @@
 
 namespace pg {
 
-#define RG_USED 1u                 // flag byte of a row: it is used
-#define RG_HEAD 2u                 //                     it starts a run
-#define RG_FIRST 1u                // flag byte of a step: first of its path
+#define RG_FIRST 1u               // flag byte of a step: first of its path
 #define RG_LAST 2u                 //                      last of its path
 #define RG_LINK 1u                 // flag byte of a sorted pair: its key differs from the pair before
 #define RG_GCHG 2u                 //                             its (key, genome) differs
@@ -465,22 +463,6 @@ struct GfaLine {
     }
   }
 };
-
-// off[0 .. n]: the flag bytes with `bit` set before each position (f[n] must be 0); returns off[n]
-struct RgBit {
-  uint32_t bit;
-  __host__ __device__ ull operator()(uint8_t f) const { return (f & bit) ? 1ull : 0ull; }
-};
-static uint64_t scan_bit(Ctx& c, const uint8_t* f, uint32_t bit, ull* off, uint64_t n) {
-  with_temp(c, [&](void* tmp, size_t& bytes) {
-    return rocprim::exclusive_scan(tmp, bytes, rocprim::make_transform_iterator(f, RgBit{bit}), off, 0ull,
-                                   (size_t)n + 1, rocprim::plus<ull>(), c.stream);
-  });
-  ull h = 0;
-  PG_HIP(hipMemcpyAsync(&h, off + n, 8, hipMemcpyDeviceToHost, c.stream));
-  c.sync();
-  return h;
-}
 
 void region_graph(Ctx& c, const int64_t* h_rows5, uint64_t n_rows, const int32_t* rec_group, uint64_t n_records,
                   uint32_t G, uint64_t* n_nodes, uint64_t* n_links, uint64_t* n_paths, uint64_t* n_skipped) {

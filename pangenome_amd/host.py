@@ -1130,6 +1130,36 @@ def write_region_seq_files(prefix: str, write_fasta, table: dict, ids, write_gfa
         whole("_fr_graph_seq.gfa", write_gfa)
 
 
+SITES_COLS = (("site_from", np.int64), ("site_to", np.int64), ("site_alleles", np.uint32), ("site_first", np.uint64),
+              ("site_count", np.uint64), ("site_genomes", np.uint32), ("allele_site", np.uint64),
+              ("allele_via", np.int64), ("allele_count", np.uint64), ("allele_genomes", np.uint32),
+              ("allele_min", np.uint64), ("allele_max", np.uint64), ("genome_sites", np.uint64),
+              ("genome_alleles", np.uint64), ("genome_private", np.uint64))
+
+
+def write_sites_files(prefix: str, write_sites, table: dict, genome_names) -> None:
+    """The three `-v` files of `prefix` (the input's path): `_fr_sites.tsv`
+    (write_sites(file) writes the text), `_fr_sites_genomes.tsv` from the
+    table's per-genome columns and `_fr_sites.npz` (every column of
+    SITES_COLS, `bits` as uint64 [alleles, W] and the genome names); each is
+    written to `.tmp` and renamed when whole."""
+    def whole(suffix, fill):
+        fn = prefix + suffix
+        with open(fn + ".tmp", "wb") as f:
+            fill(f)
+        os.replace(fn + ".tmp", fn)
+    nm = [bytes(x) for x in genome_names]
+    whole("_fr_sites.tsv", write_sites)
+    cols = [np.asarray(table[k]).tolist() for k in ("genome_sites", "genome_alleles", "genome_private")]
+    whole("_fr_sites_genomes.tsv", lambda f: f.write(b"#genome\tsites\talleles\tprivate\n" + b"".join(
+        b"%s\t%d\t%d\t%d\n" % x for x in zip(nm, *cols))))
+    arrays = {k: np.ascontiguousarray(table[k], dtype=t).reshape(-1) for k, t in SITES_COLS}
+    n = arrays["allele_site"].shape[0]
+    arrays["bits"] = np.ascontiguousarray(table["bits"], dtype=_U64).reshape(n, (len(nm) + 63) // 64)
+    arrays["genomes"] = np.array(nm, dtype=np.bytes_) if nm else np.zeros(0, "S1")
+    whole("_fr_sites.npz", lambda f: np.savez(f, **arrays))
+
+
 def seqid(name: bytes) -> bytes:
     """A record's id: its header without '>' up to the first whitespace."""
     p = bytes(name).split(None, 1)

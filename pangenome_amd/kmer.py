@@ -9,7 +9,7 @@ runs in libpangenome_hip.so on an MI355X (pangenome_amd/csrc).  Mirrors:
   dbg2rdbg     :1313-1321                rdBG (K5 degree scan + compaction)
   seq2graph    :1853-1951                edges -> .xyz -> mcl -> labels -> rows
   dump / load_on_disk  :243-335         `<in>_db.npz` (oakht slot layout)
-  entry_point  :1971-2146                CLI (-i -k -n -c -r -d -R -D; ours: -a -w -g -p -l -s)
+  entry_point  :1971-2146                CLI (-i -k -n -c -r -d -R -D; ours: -a -w -g -p -l -s -v)
 
 Usage:  python -m pangenome_amd -i genomes.fa -k 27 > result.tab
 """
@@ -257,7 +257,7 @@ def rdbg_edges(g: DeviceGraph, Ns, chunk, rc, brkpt="", keep_on_device=False):
 
 def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_dict=None, saved=None,
               hashfunc=None, jit=True, chunk=2 ** 33, rc=False, cluster=True, out=None, min_weight=1, groups=None,
-              orders=0, links=False, seqs=False, inflation2=3):
+              orders=0, links=False, seqs=False, inflation2=3, sites=False):
     """:1853-1951: edge weights -> `<qry>_rdbg_weight.xyz` -> mcl (or reuse)
     -> label dictionary -> print the region rows.  The edges, the label
     table, the rows and both texts are made on the device; the host writes
@@ -283,7 +283,10 @@ def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_
     same genomes and its four `<qry>_fr_*` files written.  seqs (-s, with
     groups): one representative sequence per label is decoded on the device
     (pg_region_seqs) and `<qry>_fr_regions.fa`, `_fr_regions.tsv` and, with
-    links, `_fr_graph_seq.gfa` written."""
+    links, `_fr_graph_seq.gfa` written.  sites (-v, with groups): the variable
+    sites of the device rows (pg_region_sites) are made with the same genomes
+    and `<qry>_fr_sites.tsv`, `_fr_sites_genomes.tsv` and `_fr_sites.npz`
+    written."""
     out = out or sys.stdout
     g = rdbg_dict
     res = rdbg_edges(g, Ns, chunk, rc, brkpt=brkpt, keep_on_device=True)
@@ -358,6 +361,8 @@ def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_
             write_region(g, qry, names, flags, groups)
         if seqs:
             write_region_seqs(g, qry, names, flags, groups, bool(links))
+        if sites:
+            write_sites(g, qry, names, flags, groups)
     gen = g.ctx.label_gen
     return LabelTable(loader=lambda: g.ctx.labels(gen))           # (raises once a later label pass replaced it)
 
@@ -444,6 +449,22 @@ def write_region_seqs(g, qry, names, flags, groups, with_graph):
     host.write_region_seq_files(qry, fasta, g.ctx.region_seqs_table(), ids, gfa if with_graph else None)
 
 
+def write_sites(g, qry, names, flags, groups):
+    """-v: the variable sites of the row pass just run (pg_region_sites on the
+    device rows, write_freq's genomes) as `<qry>_fr_sites.tsv` (the device
+    text), `_fr_sites_genomes.tsv` and `_fr_sites.npz`."""
+    rec_group, gnames = host.assign_groups(names, flags, groups)
+    g.ctx.region_sites(rec_group, len(gnames))
+    table = g.ctx.region_sites_table()
+    table.update(g.ctx.region_sites_alleles())
+    table.update(g.ctx.region_sites_groups())
+
+    def text(f):
+        f.flush()
+        g.ctx.region_sites_write(f.fileno())
+    host.write_sites_files(qry, text, table, gnames)
+
+
 def _fileno(out):
     """The descriptor under a text stream's binary buffer (stdout, a file),
     or None (a stand-in with no descriptor)."""
@@ -460,6 +481,8 @@ def manual_print(out=None):
                  "  -i: query sequences in fasta format", "  -k: kmer length",
                  "  -d: the de bruijn graph", "  -r: break point of de bruijn graph",
                  "  -D: the reduced de bruijn graph", "  -R: break point of reduced de bruijn graph",
+                 "  -v: with -g, the variable sites: pairs of regions joined in two or more ways, directly or through one region.",
+                 "      0 (off) or 1; single process only. writes <in>_fr_sites.tsv, _fr_sites_genomes.tsv, _fr_sites.npz",
                  "  -I: with -a markov, the inflation. a multiple of 0.5 from 1.5 to 20. default 1.5",
                  "  -n: length of query sequences for pan-genomic analysis",
                  "  -s: with -g, one representative sequence per region. 0 (off) or 1; single process only. writes",
@@ -481,7 +504,7 @@ def manual_print(out=None):
 def parse_args(argv):
     """:1983-1997 — same flag handling, including `-k27` and skipped unknowns."""
     args = {"-i": "", "-k": "50", "-n": "2**63", "-r": "", "-d": "", "-R": "", "-D": "", "-c": "2", "-a": "mcl",
-            "-w": "1", "-g": "", "-p": "0", "-l": "0", "-s": "0", "-I": "1.5"}
+            "-w": "1", "-g": "", "-p": "0", "-l": "0", "-s": "0", "-I": "1.5", "-v": "0"}
     N = len(argv)
     for i in range(1, N):
         k = argv[i]
@@ -548,13 +571,21 @@ def seqs_arg(args):
     return None if args["-s"] == "1" and not args["-g"] else args["-s"] == "1"
 
 
+def sites_arg(args):
+    """-v's value: False (0) or True (1), or None for a value that is refused
+    - anything else, or 1 without -g."""
+    if args["-v"] not in ("0", "1"):
+        return None
+    return None if args["-v"] == "1" and not args["-g"] else args["-v"] == "1"
+
+
 def entry_point(argv, out=None, device=0):
     out = out or sys.stdout
     args = parse_args(argv)
     qry, kmer, Ns = args["-i"], int(args["-k"]), host.eval_number(args["-n"])
     bkt, dbs, rbk, rc, rdb = args["-r"], args["-d"], args["-R"], int(args["-c"]), args["-D"]
-    n_orders, links, seqs = compare_orders_arg(args), links_arg(args), seqs_arg(args)
-    bad = not qry or n_orders is None or links is None or seqs is None
+    n_orders, links, seqs, sites = compare_orders_arg(args), links_arg(args), seqs_arg(args), sites_arg(args)
+    bad = not qry or n_orders is None or links is None or seqs is None or sites is None
     clu = None if bad else cluster_args(args)
     if clu is None:
         manual_print(out)
@@ -568,6 +599,8 @@ def entry_point(argv, out=None, device=0):
         clu["links"] = True
     if seqs:
         clu["seqs"] = True
+    if sites:
+        clu["sites"] = True
     # a group file is checked against the records before anything is built
     chk = (lambda g: check_groups(g, Ns, grp)) if grp and grp != "record" else None
     chunk = 2 ** 33
