@@ -692,7 +692,7 @@ int pg_region_gfa_seq_fd(pg_ctx* ctx, const char* names, const int64_t* name_off
  * LIMIT: only bubbles with at most one region inside are found.  An insertion
  * of two regions against a direct join is a pair (a, c) with the direct
  * allele alone and is not reported, nor is it pieced together from shorter
- * sites.
+ * sites; pg_region_bubbles, below, walks from anchor to anchor instead.
  * Alleles table, by (a, c, via) ascending - the direct allele first in its
  * site: site, the index of its site; via; count, its records; n_genomes, the
  * distinct genomes among them; min_len and max_len over their lengths; the
@@ -737,6 +737,93 @@ int pg_region_sites_groups(pg_ctx* ctx, uint64_t* sites, uint64_t* alleles, uint
  * pg_region_links_format and pg_region_links_format_fd. */
 int pg_region_sites_format(pg_ctx* ctx, char* out, uint64_t cap, uint64_t* n_bytes);
 int pg_region_sites_format_fd(pg_ctx* ctx, int fd, uint64_t* n_bytes);
+
+/* ---- variable sites between anchor regions: the bubbles of the region
+ *      graph, however many regions they span.  pg_region_sites looks through
+ *      a window of two or three rows between any two flanks; this pass walks
+ *      from one anchor to the next.  Integer only; the result depends on the
+ *      input alone, whatever the schedule.
+ * Input: exactly pg_region_sites' - rows (rows5 NULL: the last pg_rows where
+ * they lie on the device), rec_group[n_records] in [-1, n_groups), the rule
+ * for a used row, the run, and the count of the others in *n_skipped - and
+ * min_genomes, 1 <= min_genomes <= n_groups (no rows and n_groups == 0: any
+ * value >= 1, and the result is empty).
+ * Anchor: a label whose used rows lie in min_genomes distinct genomes or
+ * more (pg_freq's n_genomes of the same rows and groups; the call counts
+ * them itself and reads no pg_freq result).
+ * Segment: inside one run, two anchor steps with no anchor step between
+ * them: a, the earlier label, c, the later; the inner path, the labels of the
+ * steps strictly between them in walk order; regions, their number (0: c
+ * follows a directly); bp, the sum of |end - start| of those rows (unsigned
+ * 64-bit, as pg_freq); its genome, rec_group[record].  The steps before a
+ * run's first anchor and after its last are in no segment.  Walk order, as
+ * everywhere: no orientation is inferred.  a == c is legal.
+ * Allele of a flank pair (a, c): a distinct inner path - equal length and
+ * equal labels position by position.  Site: a flank pair with two alleles or
+ * more; a pair with one allele is dropped.
+ * Sites table, by (a, c) ascending: from = a, to = c; n_alleles; first, the
+ * index of its first allele; count, the segments over its alleles;
+ * n_genomes, the popcount of the OR of their presence sets.
+ * Alleles table, by site and inside a site by first_row ascending: site;
+ * regions; first_row, the index in the row list of the a row of the allele's
+ * earliest segment (an anchor row opens at most one segment: no ties, and
+ * the order depends on no hash); count, its segments; n_genomes; min_bp and
+ * max_bp over them; inner_off, the exclusive prefix sum of regions in table
+ * order; the presence set, W = ceil(n_groups / 64) uint64 words laid out as
+ * pg_freq_export's.
+ * Inner: int64 [sum of regions], the alleles' inner paths one after another
+ * in table order.  Per genome: sites, alleles, private, as
+ * pg_region_sites_groups defines them.  Anchors: their labels ascending, with
+ * n_genomes.
+ * Counts (each pointer may be NULL): *n_anchors, *n_segments, *n_sites,
+ * *n_alleles, *n_skipped.
+ * Exactness: the segments are grouped by (a, c), regions and a hash of the
+ * inner path - two polynomial hashes mod 2^61 - 1, one fixed function of the
+ * labels with no seed.  regions is compared before the hash, and every
+ * segment is then compared label by label, on the device, with the first
+ * segment of its group: a mismatch is PG_EDEVICE with the previous result
+ * kept, and there is no retry.  The hash only groups; identity comes from
+ * the comparison and order from first_row.
+ * PG_EINVAL, before any device work: pg_region_graph's whole list, and
+ * min_genomes out of range.  L = 1 + the largest used label > 2^31 is
+ * PG_ERANGE (found by a device reduction before anything is allocated).
+ * Nothing is dense in the label: the call takes device memory by the rows,
+ * the segments and the alleles - 9 bytes per row; per used row 29 for the
+ * steps, 33 more while the anchors are found, then 65 for the scans and the
+ * hash; per segment 168 while they are sorted, then 89, and at most 99 more
+ * per distinct (a, c, inner path) - and the tables 40 + 8 W bytes per site,
+ * 60 + 8 W per allele, 8 per inner label and 12 per label for the anchors.
+ * An allocation failure is PG_ENOMEM.  In every refusal the previous result
+ * stays: the new one is built aside and swapped in last.  The result stays
+ * until the next successful pg_region_bubbles; pg_freq, pg_freq_compare,
+ * pg_region_graph, pg_region_seqs and pg_region_sites neither read nor drop
+ * it, nor it theirs. */
+int pg_region_bubbles(pg_ctx* ctx, const int64_t* rows5, uint64_t n_rows, const int32_t* rec_group,
+                      uint64_t n_records, uint32_t n_groups, uint32_t min_genomes, uint64_t* n_anchors,
+                      uint64_t* n_segments, uint64_t* n_sites, uint64_t* n_alleles, uint64_t* n_skipped);
+/* The tables of the last pg_region_bubbles; any output pointer may be NULL;
+ * cap (entries; bits takes W words per entry) below the table's size is
+ * PG_ERANGE.  pg_region_bubbles_inner: *n_inner is the sum of regions; inner
+ * == NULL: only *n_inner is set, otherwise cap >= that, else PG_ERANGE.
+ * These and the two text calls below: PG_EINVAL before any
+ * pg_region_bubbles. */
+int pg_region_bubbles_table(pg_ctx* ctx, int64_t* from, int64_t* to, uint32_t* n_alleles, uint64_t* first,
+                            uint64_t* count, uint32_t* n_genomes, uint64_t cap);
+int pg_region_bubbles_alleles(pg_ctx* ctx, uint64_t* site, uint64_t* regions, uint64_t* first_row, uint64_t* count,
+                              uint32_t* n_genomes, uint64_t* min_bp, uint64_t* max_bp, uint64_t* inner_off,
+                              uint64_t* bits, uint64_t cap);
+int pg_region_bubbles_inner(pg_ctx* ctx, int64_t* inner, uint64_t cap, uint64_t* n_inner);
+int pg_region_bubbles_groups(pg_ctx* ctx, uint64_t* sites, uint64_t* alleles, uint64_t* private_alleles,
+                             uint64_t cap);                                  /* cap >= n_groups */
+int pg_region_bubbles_anchors(pg_ctx* ctx, int64_t* label, uint32_t* n_genomes, uint64_t cap);
+/* The alleles table's text, formatted on the device and kept there like
+ * pg_region_sites_format's: the header
+ * "#from\tto\tinner\tregions\tcount\tgenomes\tmin\tmax\n", then one line of
+ * decimals per allele in table order; inner is the labels joined by `,`, or
+ * `*` for the direct join (no sites: the header alone).  out, cap, n_bytes
+ * and the _fd form: as pg_region_sites_format and pg_region_sites_format_fd. */
+int pg_region_bubbles_format(pg_ctx* ctx, char* out, uint64_t cap, uint64_t* n_bytes);
+int pg_region_bubbles_format_fd(pg_ctx* ctx, int fd, uint64_t* n_bytes);
 
 /* ---- text output (host only; no context).  The reference formats these in
  *      Python loops (kmer_numba.py:1893-1904, :1946-1949).
@@ -864,6 +951,12 @@ uint64_t pg_format_rows(const int64_t* rows5, uint64_t n, const char* names, con
  * bucket tables).  It takes effect at the next build; pg_rdbg_export follows
  * the form of the last build.  The same keys either way. */
 #define PG_TUNE_RDBG_KEYS 24
+/* PG_TUNE_BUBBLE_HASH_BITS: pg_region_bubbles groups the segments of a flank
+ * pair by a hash of their inner paths before it compares them label by
+ * label.  0 (default) = the full hash; 1..32 = only that many low bits of one
+ * hash word, so that equal hashes of unequal paths - PG_EDEVICE from the
+ * comparison - can be tested.  The results that are returned are the same. */
+#define PG_TUNE_BUBBLE_HASH_BITS 25
 int pg_tune(pg_ctx* ctx, int what, int64_t value);
 
 /* Device bytes the library's buffers hold in this process now (peak == 0)

@@ -39,6 +39,7 @@ PG_TUNE_FREQ_FORM = 21          # pg_freq's accumulate pass: 0 aggregated in the
 PG_TUNE_CMP_CHUNK = 22          # pg_freq_compare's shared pass: label-axis words per block (0 = by size)
 PG_TUNE_CMP_FORM = 23           # pg_freq_compare's curve pass: 0 LDS counters up to 2048 genomes, 1 global atomics
 PG_TUNE_RDBG_KEYS = 24          # 0 the range pass counts rdBG members, keys swept from the table on export; 1 keys written by the build
+PG_TUNE_BUBBLE_HASH_BITS = 25   # 0 the full hash of an inner path; 1..32 its low bits only (tests of the comparison)
 
 
 class PgStats(C.Structure):
@@ -137,6 +138,15 @@ SIGNATURES = {
     "pg_region_sites_groups": (C.c_int, [_P, _P, _P, _P, C.c_uint64]),
     "pg_region_sites_format": (C.c_int, [_P, _P, C.c_uint64, _U64P]),
     "pg_region_sites_format_fd": (C.c_int, [_P, C.c_int, _U64P]),
+    "pg_region_bubbles": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, C.c_uint32, C.c_uint32, _U64P, _U64P, _U64P,
+                                    _U64P, _U64P]),
+    "pg_region_bubbles_table": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_uint64]),
+    "pg_region_bubbles_alleles": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_uint64]),
+    "pg_region_bubbles_inner": (C.c_int, [_P, _P, C.c_uint64, _U64P]),
+    "pg_region_bubbles_groups": (C.c_int, [_P, _P, _P, _P, C.c_uint64]),
+    "pg_region_bubbles_anchors": (C.c_int, [_P, _P, _P, C.c_uint64]),
+    "pg_region_bubbles_format": (C.c_int, [_P, _P, C.c_uint64, _U64P]),
+    "pg_region_bubbles_format_fd": (C.c_int, [_P, C.c_int, _U64P]),
     "pg_rows_format": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint64, _U64P]),
     "pg_rows_format_fd": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, _U64P]),
     "pg_get_stats": (C.c_int, [_P, _SP]),
@@ -980,6 +990,86 @@ class Context:
         """region_sites_text() written straight to descriptor fd at its
         position (pg_region_sites_format_fd); flush any buffered writer on fd first."""
         return _write(self.h, self.lib.pg_region_sites_format_fd, "pg_region_sites_format_fd", fd)
+
+    # ---------------------------------------------------- variable sites between anchors
+    def region_bubbles(self, rec_group, n_groups: int, min_genomes: int, rows=None):
+        """The variable sites between anchor regions (pg_region_bubbles) of
+        the last row pass where it lies on the device (rows None) or of host
+        rows [n, 5]; rec_group as region_graph() takes it; an anchor is a
+        label carried by min_genomes genomes or more.  Returns (n_anchors,
+        n_segments, n_sites, n_alleles, n_skipped); the result stays on the
+        device (region_bubbles_table / _alleles / _inner / _groups /
+        _anchors / _text and region_bubbles_write)."""
+        r5, n_rows, grp, n_records = _row_args(rec_group, rows)
+        if not 0 <= int(min_genomes) < 2 ** 32:
+            raise ValueError("min_genomes = %d does not fit the call's unsigned 32 bits" % int(min_genomes))
+        out = [C.c_uint64() for _ in range(5)]
+        check(self.lib.pg_region_bubbles(self.h, ptr(r5), n_rows, ptr(grp), n_records, int(n_groups), int(min_genomes),
+                                         *[C.byref(x) for x in out]), "pg_region_bubbles")
+        self.n_bubbles = (out[2].value, out[3].value, int(n_groups), out[0].value)
+        return tuple(x.value for x in out)
+
+    def region_bubbles_table(self) -> dict:
+        """The sites of the last region_bubbles() by (from, to) ascending:
+        site_from, site_to, site_alleles, site_first, site_count,
+        site_genomes (pg_region_bubbles_table)."""
+        n = getattr(self, "n_bubbles", (0, 0, 0, 0))[0]
+        t = {"site_from": np.empty(n, np.int64), "site_to": np.empty(n, np.int64),
+             "site_alleles": np.empty(n, np.uint32), "site_first": np.empty(n, np.uint64),
+             "site_count": np.empty(n, np.uint64), "site_genomes": np.empty(n, np.uint32)}
+        check(self.lib.pg_region_bubbles_table(self.h, *[ptr(a) for a in t.values()], n), "pg_region_bubbles_table")
+        return t
+
+    def region_bubbles_alleles(self) -> dict:
+        """The alleles by site and, inside a site, by first row: allele_site,
+        allele_regions, allele_first_row, allele_count, allele_genomes,
+        allele_min_bp, allele_max_bp, allele_inner_off and bits, uint64
+        [n, W] (pg_region_bubbles_alleles)."""
+        _, n, G, _ = getattr(self, "n_bubbles", (0, 0, 0, 0))
+        t = {"allele_site": np.empty(n, np.uint64), "allele_regions": np.empty(n, np.uint64),
+             "allele_first_row": np.empty(n, np.uint64), "allele_count": np.empty(n, np.uint64),
+             "allele_genomes": np.empty(n, np.uint32), "allele_min_bp": np.empty(n, np.uint64),
+             "allele_max_bp": np.empty(n, np.uint64), "allele_inner_off": np.empty(n, np.uint64),
+             "bits": np.empty((n, (G + 63) // 64), np.uint64)}
+        check(self.lib.pg_region_bubbles_alleles(self.h, *[ptr(a) for a in t.values()], n),
+              "pg_region_bubbles_alleles")
+        return t
+
+    def region_bubbles_inner(self) -> np.ndarray:
+        """The alleles' inner paths one after another in table order, int64
+        (pg_region_bubbles_inner); allele i's is inner[allele_inner_off[i]:][:allele_regions[i]]."""
+        n = C.c_uint64()
+        check(self.lib.pg_region_bubbles_inner(self.h, None, 0, C.byref(n)), "pg_region_bubbles_inner")
+        out = np.empty(n.value, np.int64)
+        if n.value:
+            check(self.lib.pg_region_bubbles_inner(self.h, ptr(out), n.value, C.byref(n)), "pg_region_bubbles_inner")
+        return out
+
+    def region_bubbles_groups(self) -> dict:
+        """Per genome: genome_sites, genome_alleles, genome_private
+        (pg_region_bubbles_groups)."""
+        G = getattr(self, "n_bubbles", (0, 0, 0, 0))[2]
+        t = {k: np.empty(G, np.uint64) for k in ("genome_sites", "genome_alleles", "genome_private")}
+        check(self.lib.pg_region_bubbles_groups(self.h, *[ptr(a) for a in t.values()], G), "pg_region_bubbles_groups")
+        return t
+
+    def region_bubbles_anchors(self) -> dict:
+        """The anchors, labels ascending: anchors, anchor_genomes
+        (pg_region_bubbles_anchors)."""
+        n = getattr(self, "n_bubbles", (0, 0, 0, 0))[3]
+        t = {"anchors": np.empty(n, np.int64), "anchor_genomes": np.empty(n, np.uint32)}
+        check(self.lib.pg_region_bubbles_anchors(self.h, ptr(t["anchors"]), ptr(t["anchor_genomes"]), n),
+              "pg_region_bubbles_anchors")
+        return t
+
+    def region_bubbles_text(self) -> bytes:
+        """The alleles table's text, formatted on the device (pg_region_bubbles_format)."""
+        return _text(self.h, self.lib.pg_region_bubbles_format, "pg_region_bubbles_format")
+
+    def region_bubbles_write(self, fd: int) -> int:
+        """region_bubbles_text() written straight to descriptor fd at its
+        position (pg_region_bubbles_format_fd); flush any buffered writer on fd first."""
+        return _write(self.h, self.lib.pg_region_bubbles_format_fd, "pg_region_bubbles_format_fd", fd)
 
     def rows_export(self, n: int):
         """The [n, 5] rows of the last rows_count() (pg_rows_export)."""

@@ -401,6 +401,10 @@ int pg_tune(pg_ctx* x, int what, int64_t value) {
         if (value < 0 || value > 1) throw pg::Error(PG_EINVAL, "pg_tune: rdBG keys form must be 0 or 1");
         x->c.rdbg_keys = (int)value;
         break;
+      case PG_TUNE_BUBBLE_HASH_BITS:
+        if (value < 0 || value > 32) throw pg::Error(PG_EINVAL, "pg_tune: bubble hash bits must be in [0, 32]");
+        x->c.bb_hash_bits = (int)value;
+        break;
       case PG_TUNE_STAGE_SLOTS:
         if (value < 0 || value == 1 || value > 8) throw pg::Error(PG_EINVAL, "pg_tune: staging slots must be 0 or 2..8");
         x->c.stage_slots = value ? (uint64_t)value : 4;
@@ -1062,6 +1066,76 @@ int pg_region_sites_format_fd(pg_ctx* x, int fd, uint64_t* n_bytes) {
     if (!x || !n_bytes || fd < 0) throw pg::Error(PG_EINVAL, "pg_region_sites_format_fd: bad arguments");
     PG_HIP(hipSetDevice(x->c.device));
     *n_bytes = pg::format_region_sites(x->c, nullptr, 0, fd);
+  });
+}
+
+int pg_region_bubbles(pg_ctx* x, const int64_t* rows5, uint64_t n_rows, const int32_t* rec_group, uint64_t n_records,
+                      uint32_t n_groups, uint32_t min_genomes, uint64_t* n_anchors, uint64_t* n_segments,
+                      uint64_t* n_sites, uint64_t* n_alleles, uint64_t* n_skipped) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_region_bubbles: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::region_bubbles(x->c, rows5, n_rows, rec_group, n_records, n_groups, min_genomes, n_anchors, n_segments,
+                       n_sites, n_alleles, n_skipped);
+  });
+}
+
+int pg_region_bubbles_table(pg_ctx* x, int64_t* from, int64_t* to, uint32_t* n_alleles, uint64_t* first,
+                            uint64_t* count, uint32_t* n_genomes, uint64_t cap) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_region_bubbles_table: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::region_bubbles_table(x->c, from, to, n_alleles, first, count, n_genomes, cap);
+  });
+}
+
+int pg_region_bubbles_alleles(pg_ctx* x, uint64_t* site, uint64_t* regions, uint64_t* first_row, uint64_t* count,
+                              uint32_t* n_genomes, uint64_t* min_bp, uint64_t* max_bp, uint64_t* inner_off,
+                              uint64_t* bits, uint64_t cap) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_region_bubbles_alleles: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::region_bubbles_alleles(x->c, site, regions, first_row, count, n_genomes, min_bp, max_bp, inner_off, bits, cap);
+  });
+}
+
+int pg_region_bubbles_inner(pg_ctx* x, int64_t* inner, uint64_t cap, uint64_t* n_inner) {
+  return guard([&] {
+    if (!x || !n_inner) throw pg::Error(PG_EINVAL, "pg_region_bubbles_inner: bad arguments");
+    PG_HIP(hipSetDevice(x->c.device));
+    *n_inner = pg::region_bubbles_inner(x->c, inner, cap);
+  });
+}
+
+int pg_region_bubbles_groups(pg_ctx* x, uint64_t* sites, uint64_t* alleles, uint64_t* private_alleles, uint64_t cap) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_region_bubbles_groups: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::region_bubbles_groups(x->c, sites, alleles, private_alleles, cap);
+  });
+}
+
+int pg_region_bubbles_anchors(pg_ctx* x, int64_t* label, uint32_t* n_genomes, uint64_t cap) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_region_bubbles_anchors: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::region_bubbles_anchors(x->c, label, n_genomes, cap);
+  });
+}
+
+int pg_region_bubbles_format(pg_ctx* x, char* out, uint64_t cap, uint64_t* n_bytes) {
+  return guard([&] {
+    if (!x || !n_bytes) throw pg::Error(PG_EINVAL, "pg_region_bubbles_format: bad arguments");
+    PG_HIP(hipSetDevice(x->c.device));
+    *n_bytes = pg::format_region_bubbles(x->c, out, cap);
+  });
+}
+
+int pg_region_bubbles_format_fd(pg_ctx* x, int fd, uint64_t* n_bytes) {
+  return guard([&] {
+    if (!x || !n_bytes || fd < 0) throw pg::Error(PG_EINVAL, "pg_region_bubbles_format_fd: bad arguments");
+    PG_HIP(hipSetDevice(x->c.device));
+    *n_bytes = pg::format_region_bubbles(x->c, nullptr, 0, fd);
   });
 }
 

@@ -350,6 +350,18 @@ struct Ctx {
   uint64_t vs_ns = 0, vs_na = 0, vs_total = 0;
   uint32_t vs_groups = 0, vs_words = 0;
   bool vs_ready = false;
+  // ---- variable sites between anchors (pg_bubbles.hip): the result of the last pg_region_bubbles
+  DevBuf bb_sites;                // [n] from, to, first, count; uint32 [n] alleles, genomes
+  DevBuf bb_alleles;              // [n + 1] site, regions, first row, count, min, max, inner offset; uint32 [n] genomes
+  DevBuf bb_bits;                 // [alleles][W] presence words
+  DevBuf bb_inner;                // the alleles' inner paths one after another
+  DevBuf bb_grp;                  // [3][G]: sites, alleles, private per genome
+  DevBuf bb_anchors;              // [n] label; uint32 [n] genomes
+  DevBuf bb_text;                 // the alleles' text
+  uint64_t bb_ns = 0, bb_na = 0, bb_nin = 0, bb_nanc = 0, bb_total = 0;
+  uint32_t bb_groups = 0, bb_words = 0;
+  bool bb_ready = false;
+  int bb_hash_bits = 0;           // pg_tune: low bits kept of the inner path's hash (0 = all of it)
 
   // ---- npz persistence (pg_persist.hip)
   DevBuf preload;                 // staged PreEnt pairs, OR-merged by every build
@@ -609,6 +621,25 @@ void region_sites_alleles(Ctx& c, uint64_t* site, int64_t* via, uint64_t* count,
                           uint64_t* min_len, uint64_t* max_len, uint64_t* bits, uint64_t cap);
 void region_sites_groups(Ctx& c, uint64_t* sites, uint64_t* alleles, uint64_t* private_, uint64_t cap);
 uint64_t format_region_sites(Ctx& c, char* out, uint64_t cap, int fd = -1);
+
+// pg_bubbles.hip
+// The variable sites between anchor regions of rows (h_rows5 NULL: the last
+// row pass) grouped by rec_group: the pairs of anchors - labels carried by
+// min_genomes genomes or more - that two or more inner paths join; replaces
+// the context's previous bubbles only when it succeeds.
+#define NEED_BUBBLES "no bubbles (call pg_region_bubbles first)"
+void region_bubbles(Ctx& c, const int64_t* h_rows5, uint64_t n_rows, const int32_t* rec_group, uint64_t n_records,
+                    uint32_t n_groups, uint32_t min_genomes, uint64_t* n_anchors, uint64_t* n_segments,
+                    uint64_t* n_sites, uint64_t* n_alleles, uint64_t* n_skipped);
+void region_bubbles_table(Ctx& c, int64_t* from, int64_t* to, uint32_t* n_alleles, uint64_t* first, uint64_t* count,
+                          uint32_t* n_genomes, uint64_t cap);
+void region_bubbles_alleles(Ctx& c, uint64_t* site, uint64_t* regions, uint64_t* first_row, uint64_t* count,
+                            uint32_t* n_genomes, uint64_t* min_bp, uint64_t* max_bp, uint64_t* inner_off,
+                            uint64_t* bits, uint64_t cap);
+uint64_t region_bubbles_inner(Ctx& c, int64_t* inner, uint64_t cap);
+void region_bubbles_groups(Ctx& c, uint64_t* sites, uint64_t* alleles, uint64_t* private_, uint64_t cap);
+void region_bubbles_anchors(Ctx& c, int64_t* label, uint32_t* n_genomes, uint64_t cap);
+uint64_t format_region_bubbles(Ctx& c, char* out, uint64_t cap, int fd = -1);
 
 // helpers
 inline uint64_t next_pow2(uint64_t x) {

@@ -1160,6 +1160,39 @@ def write_sites_files(prefix: str, write_sites, table: dict, genome_names) -> No
     whole("_fr_sites.npz", lambda f: np.savez(f, **arrays))
 
 
+BUBBLES_COLS = (("site_from", np.int64), ("site_to", np.int64), ("site_alleles", np.uint32),
+                ("site_first", np.uint64), ("site_count", np.uint64), ("site_genomes", np.uint32),
+                ("allele_site", np.uint64), ("allele_regions", np.uint64), ("allele_first_row", np.uint64),
+                ("allele_count", np.uint64), ("allele_genomes", np.uint32), ("allele_min_bp", np.uint64),
+                ("allele_max_bp", np.uint64), ("allele_inner_off", np.uint64), ("inner", np.int64),
+                ("genome_sites", np.uint64), ("genome_alleles", np.uint64), ("genome_private", np.uint64),
+                ("anchors", np.int64), ("anchor_genomes", np.uint32))
+
+
+def write_bubbles_files(prefix: str, write_bubbles, table: dict, genome_names, min_genomes: int) -> None:
+    """The three `-b` files of `prefix` (the input's path): `_fr_bubbles.tsv`
+    (write_bubbles(file) writes the text), `_fr_bubbles_genomes.tsv` from the
+    table's per-genome columns and `_fr_bubbles.npz` (every column of
+    BUBBLES_COLS, `bits` as uint64 [alleles, W], the genome names and
+    min_genomes); each is written to `.tmp` and renamed when whole."""
+    def whole(suffix, fill):
+        fn = prefix + suffix
+        with open(fn + ".tmp", "wb") as f:
+            fill(f)
+        os.replace(fn + ".tmp", fn)
+    nm = [bytes(x) for x in genome_names]
+    whole("_fr_bubbles.tsv", write_bubbles)
+    cols = [np.asarray(table[k]).tolist() for k in ("genome_sites", "genome_alleles", "genome_private")]
+    whole("_fr_bubbles_genomes.tsv", lambda f: f.write(b"#genome\tsites\talleles\tprivate\n" + b"".join(
+        b"%s\t%d\t%d\t%d\n" % x for x in zip(nm, *cols))))
+    arrays = {k: np.ascontiguousarray(table[k], dtype=t).reshape(-1) for k, t in BUBBLES_COLS}
+    n = arrays["allele_site"].shape[0]
+    arrays["bits"] = np.ascontiguousarray(table["bits"], dtype=_U64).reshape(n, (len(nm) + 63) // 64)
+    arrays["genomes"] = np.array(nm, dtype=np.bytes_) if nm else np.zeros(0, "S1")
+    arrays["min_genomes"] = np.array(int(min_genomes), np.int64)
+    whole("_fr_bubbles.npz", lambda f: np.savez(f, **arrays))
+
+
 def seqid(name: bytes) -> bytes:
     """A record's id: its header without '>' up to the first whitespace."""
     p = bytes(name).split(None, 1)

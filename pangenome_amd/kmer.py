@@ -257,7 +257,7 @@ def rdbg_edges(g: DeviceGraph, Ns, chunk, rc, brkpt="", keep_on_device=False):
 
 def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_dict=None, saved=None,
               hashfunc=None, jit=True, chunk=2 ** 33, rc=False, cluster=True, out=None, min_weight=1, groups=None,
-              orders=0, links=False, seqs=False, inflation2=3, sites=False):
+              orders=0, links=False, seqs=False, inflation2=3, sites=False, bubbles=0):
     """:1853-1951: edge weights -> `<qry>_rdbg_weight.xyz` -> mcl (or reuse)
     -> label dictionary -> print the region rows.  The edges, the label
     table, the rows and both texts are made on the device; the host writes
@@ -286,7 +286,10 @@ def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_
     links, `_fr_graph_seq.gfa` written.  sites (-v, with groups): the variable
     sites of the device rows (pg_region_sites) are made with the same genomes
     and `<qry>_fr_sites.tsv`, `_fr_sites_genomes.tsv` and `_fr_sites.npz`
-    written."""
+    written.  bubbles (-b, with groups; 0: off): the variable sites between
+    anchor regions - labels carried by that many genomes, at most all of them
+    - are made the same way (pg_region_bubbles) and `<qry>_fr_bubbles.tsv`,
+    `_fr_bubbles_genomes.tsv` and `_fr_bubbles.npz` written."""
     out = out or sys.stdout
     g = rdbg_dict
     res = rdbg_edges(g, Ns, chunk, rc, brkpt=brkpt, keep_on_device=True)
@@ -363,6 +366,8 @@ def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_
             write_region_seqs(g, qry, names, flags, groups, bool(links))
         if sites:
             write_sites(g, qry, names, flags, groups)
+        if bubbles:
+            write_bubbles(g, qry, names, flags, groups, int(bubbles))
     gen = g.ctx.label_gen
     return LabelTable(loader=lambda: g.ctx.labels(gen))           # (raises once a later label pass replaced it)
 
@@ -465,6 +470,27 @@ def write_sites(g, qry, names, flags, groups):
     host.write_sites_files(qry, text, table, gnames)
 
 
+def write_bubbles(g, qry, names, flags, groups, min_genomes):
+    """-b: the variable sites between anchor regions of the row pass just run
+    (pg_region_bubbles on the device rows, write_freq's genomes; an anchor is
+    a label in min_genomes genomes, at most all of them) as
+    `<qry>_fr_bubbles.tsv` (the device text), `_fr_bubbles_genomes.tsv` and
+    `_fr_bubbles.npz`."""
+    rec_group, gnames = host.assign_groups(names, flags, groups)
+    m = max(1, min(int(min_genomes), len(gnames)))
+    g.ctx.region_bubbles(rec_group, len(gnames), m)
+    table = g.ctx.region_bubbles_table()
+    table.update(g.ctx.region_bubbles_alleles())
+    table["inner"] = g.ctx.region_bubbles_inner()
+    table.update(g.ctx.region_bubbles_groups())
+    table.update(g.ctx.region_bubbles_anchors())
+
+    def text(f):
+        f.flush()
+        g.ctx.region_bubbles_write(f.fileno())
+    host.write_bubbles_files(qry, text, table, gnames, m)
+
+
 def _fileno(out):
     """The descriptor under a text stream's binary buffer (stdout, a file),
     or None (a stand-in with no descriptor)."""
@@ -484,6 +510,8 @@ def manual_print(out=None):
                  "  -v: with -g, the variable sites: pairs of regions joined in two or more ways, directly or through one region.",
                  "      0 (off) or 1; single process only. writes <in>_fr_sites.tsv, _fr_sites_genomes.tsv, _fr_sites.npz",
                  "  -I: with -a markov, the inflation. a multiple of 0.5 from 1.5 to 20. default 1.5",
+                 "  -b: with -g, the variable sites between anchors, regions found in at least this many genomes (0: off), however",
+                 "      many regions lie between two. single process only. writes <in>_fr_bubbles.tsv, _fr_bubbles_genomes.tsv, _fr_bubbles.npz",
                  "  -n: length of query sequences for pan-genomic analysis",
                  "  -s: with -g, one representative sequence per region. 0 (off) or 1; single process only. writes",
                  "      <in>_fr_regions.fa, _fr_regions.tsv and, with -l 1, _fr_graph_seq.gfa (GFA 1 with sequences)",
@@ -504,7 +532,7 @@ def manual_print(out=None):
 def parse_args(argv):
     """:1983-1997 — same flag handling, including `-k27` and skipped unknowns."""
     args = {"-i": "", "-k": "50", "-n": "2**63", "-r": "", "-d": "", "-R": "", "-D": "", "-c": "2", "-a": "mcl",
-            "-w": "1", "-g": "", "-p": "0", "-l": "0", "-s": "0", "-I": "1.5", "-v": "0"}
+            "-w": "1", "-g": "", "-p": "0", "-l": "0", "-s": "0", "-I": "1.5", "-v": "0", "-b": "0"}
     N = len(argv)
     for i in range(1, N):
         k = argv[i]
@@ -579,13 +607,23 @@ def sites_arg(args):
     return None if args["-v"] == "1" and not args["-g"] else args["-v"] == "1"
 
 
+def bubbles_arg(args):
+    """-b's value: min_genomes (0: off), or None for a value that is refused
+    - not a non-negative decimal integer, or >= 1 without -g."""
+    if not args["-b"].isascii() or not args["-b"].isdigit():
+        return None
+    b = int(args["-b"])
+    return None if b and not args["-g"] else b
+
+
 def entry_point(argv, out=None, device=0):
     out = out or sys.stdout
     args = parse_args(argv)
     qry, kmer, Ns = args["-i"], int(args["-k"]), host.eval_number(args["-n"])
     bkt, dbs, rbk, rc, rdb = args["-r"], args["-d"], args["-R"], int(args["-c"]), args["-D"]
     n_orders, links, seqs, sites = compare_orders_arg(args), links_arg(args), seqs_arg(args), sites_arg(args)
-    bad = not qry or n_orders is None or links is None or seqs is None or sites is None
+    bubbles = bubbles_arg(args)
+    bad = not qry or n_orders is None or links is None or seqs is None or sites is None or bubbles is None
     clu = None if bad else cluster_args(args)
     if clu is None:
         manual_print(out)
@@ -601,6 +639,8 @@ def entry_point(argv, out=None, device=0):
         clu["seqs"] = True
     if sites:
         clu["sites"] = True
+    if bubbles:
+        clu["bubbles"] = bubbles
     # a group file is checked against the records before anything is built
     chk = (lambda g: check_groups(g, Ns, grp)) if grp and grp != "record" else None
     chunk = 2 ** 33
