@@ -797,7 +797,8 @@ int pg_region_sites_format_fd(pg_ctx* ctx, int fd, uint64_t* n_bytes);
  * stays: the new one is built aside and swapped in last.  The result stays
  * until the next successful pg_region_bubbles; pg_freq, pg_freq_compare,
  * pg_region_graph, pg_region_seqs and pg_region_sites neither read nor drop
- * it, nor it theirs. */
+ * it, nor it theirs.  (pg_region_variants, below, reads it; a successful
+ * pg_region_bubbles drops the variants.) */
 int pg_region_bubbles(pg_ctx* ctx, const int64_t* rows5, uint64_t n_rows, const int32_t* rec_group,
                       uint64_t n_records, uint32_t n_groups, uint32_t min_genomes, uint64_t* n_anchors,
                       uint64_t* n_segments, uint64_t* n_sites, uint64_t* n_alleles, uint64_t* n_skipped);
@@ -824,6 +825,103 @@ int pg_region_bubbles_anchors(pg_ctx* ctx, int64_t* label, uint32_t* n_genomes, 
  * and the _fd form: as pg_region_sites_format and pg_region_sites_format_fd. */
 int pg_region_bubbles_format(pg_ctx* ctx, char* out, uint64_t cap, uint64_t* n_bytes);
 int pg_region_bubbles_format_fd(pg_ctx* ctx, int fd, uint64_t* n_bytes);
+
+/* ---- the bubbles' alleles as sequences, and the sites placed on a reference
+ *      genome: the tables, an allele FASTA and the body of a VCF.  Integer
+ *      only; the result depends on the input alone, whatever the schedule.
+ * Input: exactly pg_region_bubbles' rows (rows5 NULL: the last pg_rows where
+ * they lie on the device), rec_group, the rule for a used row and the run;
+ * n_records is the context's record count in both forms, because the bases
+ * come from the context's parse; and the context's last pg_region_bubbles
+ * result, which must describe these rows and groups.  lo(r) = min(start,
+ * end), hi(r) = max(start, end).
+ * Segment at row i, a used row whose label is an anchor: j > i is the next row
+ * of i's run whose label is an anchor; flanks (label[i], label[j]), inner
+ * path the labels of rows i + 1 .. j - 1.  Its span: bases [hi(i), lo(j)) of
+ * the record's compacted sequence if strand == 1, otherwise [hi(j), lo(i));
+ * its sequence: those bases, one letter per base class as pg_region_seqs (A C
+ * G T, everything else N), as they stand if strand == 1 and reverse
+ * complemented otherwise, so that every allele reads in walk direction.
+ * Allele t's sequence is that of the segment at row first_row[t] (its c row
+ * is first_row + regions + 1); a direct join may have length 0.  Two alleles
+ * of a site may read the same - different label paths can have the same bases
+ * - and they are not merged.
+ * Allele table, in the bubbles alleles' order: record; lo, hi, the span;
+ * strand; len; gc and amb as pg_region_seqs; offset, the exclusive prefix sum
+ * of len.  The bases are the sequences one after another without separators;
+ * *n_bases is the sum of len.
+ * Reference placement: ref_group in [0, n_groups), or PG_NO_REF, which places
+ * nothing.  The reference segment of site s is the segment with s's flank
+ * pair in a record of genome ref_group on strand == 1 with the smallest row
+ * index i.  Its inner path equals exactly one allele of s: ref_allele, an
+ * index inside the site.  pos0 = hi(row i), ref_len its span's length.  A site
+ * is placed iff it has a reference segment and pos0 >= 1, so that a padding
+ * base exists; the others are unplaced.
+ * Placed table, by (record, pos0, site index) ascending: site, record, pos0,
+ * ref_row, ref_allele, ref_len.
+ * Counts (each pointer may be NULL): *n_alleles, *n_bases, *n_placed,
+ * *n_unplaced.
+ * PG_EINVAL, before anything is replaced: pg_region_bubbles' whole list; no
+ * bubbles result; n_groups other than the bubbles result's; ref_group >=
+ * n_groups and not PG_NO_REF; a context without a parse, or another record
+ * count; a used row with lo < 0 or hi past its record; an allele whose rows
+ * first_row .. first_row + regions + 1 do not match the bubbles result (inside
+ * the list, all used, one record and strand, labels equal to from, the inner
+ * path and to: checked on the device, one thread per step); a representative
+ * or reference segment whose flank rows overlap or are out of order (span
+ * start > end); a reference segment that matches no allele.  An allocation
+ * failure is PG_ENOMEM.  In every refusal the previous result stays.
+ * Device memory while the call runs: 1 byte per row (and 40 for rows from the
+ * host), 97 per allele, 45 per site and 32 more per placed site; the result
+ * holds 88 per allele, 132 per placed site and 1 per base, every sequence
+ * (and every placed site's padding base + REF) starting at a multiple of 16.
+ * Lifetime: the texts read the bubbles tables when they are formatted, so a
+ * later successful pg_region_bubbles drops the result (as pg_freq drops the
+ * comparison) and the exports below return PG_EINVAL again; no other pass
+ * reads or drops it. */
+#define PG_NO_REF UINT32_MAX
+int pg_region_variants(pg_ctx* ctx, const int64_t* rows5, uint64_t n_rows, const int32_t* rec_group,
+                       uint64_t n_records, uint32_t n_groups, uint32_t ref_group, uint64_t* n_alleles,
+                       uint64_t* n_bases, uint64_t* n_placed, uint64_t* n_unplaced);
+/* The tables of the last pg_region_variants; any output pointer may be NULL;
+ * cap (entries) below the table's size is PG_ERANGE.
+ * pg_region_variants_bases: *n_bytes = n_bases; out == NULL: only that,
+ * otherwise cap >= n_bases, else PG_ERANGE.  pg_region_variants_time: the
+ * decoder kernel's time (HIP events) and its 16-letter chunks, the placed
+ * sites' padding base + REF included.  All of these and the text calls below:
+ * PG_EINVAL before any pg_region_variants. */
+int pg_region_variants_alleles(pg_ctx* ctx, int64_t* record, int64_t* lo, int64_t* hi, int64_t* strand,
+                               uint64_t* len, uint64_t* gc, uint64_t* amb, uint64_t* offset, uint64_t cap);
+int pg_region_variants_bases(pg_ctx* ctx, uint8_t* out, uint64_t cap, uint64_t* n_bytes);
+int pg_region_variants_placed(pg_ctx* ctx, uint64_t* site, int64_t* record, int64_t* pos0, uint64_t* ref_row,
+                              uint32_t* ref_allele, uint64_t* ref_len, uint64_t cap);
+int pg_region_variants_time(pg_ctx* ctx, double* ms_decode, uint64_t* n_chunks);
+/* The allele FASTA, formatted on the device by every call with its own record
+ * names: per allele in table order, k its index inside its site,
+ *   ><from>_<to>_<k> <name>:<lo>-<hi>:<+|-> regions=<r> genomes=<g> len=<len>\n<sequence>\n
+ * (a direct join of length 0 gives an empty sequence line).  names, out, cap,
+ * n_bytes and the _fd form: as pg_region_gfa and pg_region_gfa_fd; n_names
+ * must cover the context's records. */
+int pg_region_alleles_fasta(pg_ctx* ctx, const char* names, const int64_t* name_off, uint64_t n_names, char* out,
+                            uint64_t cap, uint64_t* n_bytes);
+int pg_region_alleles_fasta_fd(pg_ctx* ctx, const char* names, const int64_t* name_off, uint64_t n_names, int fd,
+                               uint64_t* n_bytes);
+/* The VCF body: one line per placed site in the placed table's order,
+ * tab separated and newline ended (no placed site: empty):
+ *   <names[record]> <pos0> <from>_<to> <REF> <ALT> . . NS=<site n_genomes> GT <cell g = 0> ... <cell g = G - 1>
+ * pad is the letter of reference base pos0 - 1, and POS = pos0 its 1-based
+ * coordinate.  REF = pad + the reference record's own letters [pos0, pos0 +
+ * ref_len) - the reference's bases, not the ref allele's representative.  ALT:
+ * one entry pad + sequence for every other allele of the site in table order,
+ * joined by `,`.  The ref allele is number 0, the others 1, 2, ... in table
+ * order; the cell of genome g lists the numbers of the alleles whose presence
+ * bit g is set, ascending, joined by `/`, or `.` if there are none.  Equal
+ * allele strings are not merged.  The caller writes the header lines.  The
+ * arguments: as pg_region_alleles_fasta. */
+int pg_region_vcf(pg_ctx* ctx, const char* names, const int64_t* name_off, uint64_t n_names, char* out, uint64_t cap,
+                  uint64_t* n_bytes);
+int pg_region_vcf_fd(pg_ctx* ctx, const char* names, const int64_t* name_off, uint64_t n_names, int fd,
+                     uint64_t* n_bytes);
 
 /* ---- text output (host only; no context).  The reference formats these in
  *      Python loops (kmer_numba.py:1893-1904, :1946-1949).

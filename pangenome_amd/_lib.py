@@ -147,6 +147,16 @@ SIGNATURES = {
     "pg_region_bubbles_anchors": (C.c_int, [_P, _P, _P, C.c_uint64]),
     "pg_region_bubbles_format": (C.c_int, [_P, _P, C.c_uint64, _U64P]),
     "pg_region_bubbles_format_fd": (C.c_int, [_P, C.c_int, _U64P]),
+    "pg_region_variants": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, C.c_uint32, C.c_uint32, _U64P, _U64P, _U64P,
+                                     _U64P]),
+    "pg_region_variants_alleles": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_uint64]),
+    "pg_region_variants_bases": (C.c_int, [_P, _P, C.c_uint64, _U64P]),
+    "pg_region_variants_placed": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_uint64]),
+    "pg_region_variants_time": (C.c_int, [_P, C.POINTER(C.c_double), _U64P]),
+    "pg_region_alleles_fasta": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint64, _U64P]),
+    "pg_region_alleles_fasta_fd": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, _U64P]),
+    "pg_region_vcf": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint64, _U64P]),
+    "pg_region_vcf_fd": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, _U64P]),
     "pg_rows_format": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint64, _U64P]),
     "pg_rows_format_fd": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, _U64P]),
     "pg_get_stats": (C.c_int, [_P, _SP]),
@@ -1070,6 +1080,81 @@ class Context:
         """region_bubbles_text() written straight to descriptor fd at its
         position (pg_region_bubbles_format_fd); flush any buffered writer on fd first."""
         return _write(self.h, self.lib.pg_region_bubbles_format_fd, "pg_region_bubbles_format_fd", fd)
+
+    # ---------------------------------------------------- the bubbles' alleles as sequences, the VCF
+    NO_REF = 2 ** 32 - 1
+
+    def region_variants(self, rec_group, n_groups: int, ref_group=None, rows=None):
+        """The bases of every allele of the last region_bubbles() and the
+        sites placed on the walks of genome ref_group (None: PG_NO_REF, no
+        site is placed) (pg_region_variants); rows and rec_group must be the
+        ones region_bubbles() took.  Returns (n_alleles, n_bases, n_placed,
+        n_unplaced); the result stays on the device (region_variants_alleles
+        / _bases / _placed, region_alleles_fasta_text, region_vcf_text and
+        their _write forms) until the next region_bubbles()."""
+        r5, n_rows, grp, n_records = _row_args(rec_group, rows)
+        ref = self.NO_REF if ref_group is None else int(ref_group)
+        if not 0 <= ref < 2 ** 32:
+            raise ValueError("ref_group = %d does not fit the call's unsigned 32 bits" % ref)
+        out = [C.c_uint64() for _ in range(4)]
+        check(self.lib.pg_region_variants(self.h, ptr(r5), n_rows, ptr(grp), n_records, int(n_groups), ref,
+                                          *[C.byref(x) for x in out]), "pg_region_variants")
+        self.n_variants = (out[0].value, out[2].value)
+        return tuple(x.value for x in out)
+
+    def region_variants_alleles(self) -> dict:
+        """The allele table in the bubbles alleles' order: record, lo, hi,
+        strand (int64), len, gc, amb, offset (uint64) (pg_region_variants_alleles)."""
+        n = getattr(self, "n_variants", (0, 0))[0]
+        t = {k: np.empty(n, np.int64) for k in ("record", "lo", "hi", "strand")}
+        t.update({k: np.empty(n, np.uint64) for k in ("len", "gc", "amb", "offset")})
+        check(self.lib.pg_region_variants_alleles(self.h, *[ptr(a) for a in t.values()], n),
+              "pg_region_variants_alleles")
+        return t
+
+    def region_variants_bases(self) -> bytes:
+        """The alleles' sequences one after another in table order, no
+        separators (pg_region_variants_bases)."""
+        return _text(self.h, self.lib.pg_region_variants_bases, "pg_region_variants_bases")
+
+    def region_variants_placed(self) -> dict:
+        """The placed sites by (record, pos0, site) ascending: site, record,
+        pos0, ref_row, ref_allele, ref_len (pg_region_variants_placed)."""
+        n = getattr(self, "n_variants", (0, 0))[1]
+        t = {"site": np.empty(n, np.uint64), "record": np.empty(n, np.int64), "pos0": np.empty(n, np.int64),
+             "ref_row": np.empty(n, np.uint64), "ref_allele": np.empty(n, np.uint32),
+             "ref_len": np.empty(n, np.uint64)}
+        check(self.lib.pg_region_variants_placed(self.h, *[ptr(a) for a in t.values()], n),
+              "pg_region_variants_placed")
+        return t
+
+    def region_variants_time(self):
+        """(ms, chunks): the decoder kernel's time in the last
+        region_variants() and the 16-letter chunks it wrote (pg_region_variants_time)."""
+        ms, n = C.c_double(), C.c_uint64()
+        check(self.lib.pg_region_variants_time(self.h, C.byref(ms), C.byref(n)), "pg_region_variants_time")
+        return ms.value, n.value
+
+    def region_alleles_fasta_text(self, names: list) -> bytes:
+        """The alleles as FASTA, formatted on the device
+        (pg_region_alleles_fasta); names[r] = record r's name."""
+        return _text(self.h, self.lib.pg_region_alleles_fasta, "pg_region_alleles_fasta", *_names_args(names))
+
+    def region_alleles_fasta_write(self, names: list, fd: int) -> int:
+        """region_alleles_fasta_text(names) written straight to descriptor fd
+        at its position (pg_region_alleles_fasta_fd); flush any buffered writer on fd first."""
+        return _write(self.h, self.lib.pg_region_alleles_fasta_fd, "pg_region_alleles_fasta_fd", fd,
+                      *_names_args(names))
+
+    def region_vcf_text(self, names: list) -> bytes:
+        """The VCF body, one line per placed site, formatted on the device
+        (pg_region_vcf); names[r] = record r's name, the CHROM column."""
+        return _text(self.h, self.lib.pg_region_vcf, "pg_region_vcf", *_names_args(names))
+
+    def region_vcf_write(self, names: list, fd: int) -> int:
+        """region_vcf_text(names) written straight to descriptor fd at its
+        position (pg_region_vcf_fd); flush any buffered writer on fd first."""
+        return _write(self.h, self.lib.pg_region_vcf_fd, "pg_region_vcf_fd", fd, *_names_args(names))
 
     def rows_export(self, n: int):
         """The [n, 5] rows of the last rows_count() (pg_rows_export)."""

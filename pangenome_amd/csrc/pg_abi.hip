@@ -1139,6 +1139,88 @@ int pg_region_bubbles_format_fd(pg_ctx* x, int fd, uint64_t* n_bytes) {
   });
 }
 
+int pg_region_variants(pg_ctx* x, const int64_t* rows5, uint64_t n_rows, const int32_t* rec_group, uint64_t n_records,
+                       uint32_t n_groups, uint32_t ref_group, uint64_t* n_alleles, uint64_t* n_bases,
+                       uint64_t* n_placed, uint64_t* n_unplaced) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_region_variants: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::region_variants(x->c, rows5, n_rows, rec_group, n_records, n_groups, ref_group, n_alleles, n_bases, n_placed,
+                        n_unplaced);
+  });
+}
+
+int pg_region_variants_alleles(pg_ctx* x, int64_t* record, int64_t* lo, int64_t* hi, int64_t* strand, uint64_t* len,
+                               uint64_t* gc, uint64_t* amb, uint64_t* offset, uint64_t cap) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_region_variants_alleles: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::region_variants_alleles(x->c, record, lo, hi, strand, len, gc, amb, offset, cap);
+  });
+}
+
+int pg_region_variants_bases(pg_ctx* x, uint8_t* out, uint64_t cap, uint64_t* n_bytes) {
+  return guard([&] {
+    if (!x || !n_bytes) throw pg::Error(PG_EINVAL, "pg_region_variants_bases: bad arguments");
+    PG_HIP(hipSetDevice(x->c.device));
+    *n_bytes = pg::region_variants_bases(x->c, out, cap);
+  });
+}
+
+int pg_region_variants_placed(pg_ctx* x, uint64_t* site, int64_t* record, int64_t* pos0, uint64_t* ref_row,
+                              uint32_t* ref_allele, uint64_t* ref_len, uint64_t cap) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_region_variants_placed: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::region_variants_placed(x->c, site, record, pos0, ref_row, ref_allele, ref_len, cap);
+  });
+}
+
+int pg_region_variants_time(pg_ctx* x, double* ms_decode, uint64_t* n_chunks) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_region_variants_time: ctx is NULL");
+    if (!x->c.vr_ready) throw pg::Error(PG_EINVAL, std::string("pg_region_variants_time: ") + NEED_VARIANTS);
+    if (ms_decode) *ms_decode = x->c.ms_vr_decode;
+    if (n_chunks) *n_chunks = x->c.vr_chunks;
+  });
+}
+
+int pg_region_alleles_fasta(pg_ctx* x, const char* names, const int64_t* name_off, uint64_t n_names, char* out,
+                            uint64_t cap, uint64_t* n_bytes) {
+  return guard([&] {
+    if (!x || !n_bytes) throw pg::Error(PG_EINVAL, "pg_region_alleles_fasta: bad arguments");
+    PG_HIP(hipSetDevice(x->c.device));
+    *n_bytes = pg::format_region_alleles_fasta(x->c, names, name_off, n_names, out, cap);
+  });
+}
+
+int pg_region_alleles_fasta_fd(pg_ctx* x, const char* names, const int64_t* name_off, uint64_t n_names, int fd,
+                               uint64_t* n_bytes) {
+  return guard([&] {
+    if (!x || !n_bytes || fd < 0) throw pg::Error(PG_EINVAL, "pg_region_alleles_fasta_fd: bad arguments");
+    PG_HIP(hipSetDevice(x->c.device));
+    *n_bytes = pg::format_region_alleles_fasta(x->c, names, name_off, n_names, nullptr, 0, fd);
+  });
+}
+
+int pg_region_vcf(pg_ctx* x, const char* names, const int64_t* name_off, uint64_t n_names, char* out, uint64_t cap,
+                  uint64_t* n_bytes) {
+  return guard([&] {
+    if (!x || !n_bytes) throw pg::Error(PG_EINVAL, "pg_region_vcf: bad arguments");
+    PG_HIP(hipSetDevice(x->c.device));
+    *n_bytes = pg::format_region_vcf(x->c, names, name_off, n_names, out, cap);
+  });
+}
+
+int pg_region_vcf_fd(pg_ctx* x, const char* names, const int64_t* name_off, uint64_t n_names, int fd,
+                     uint64_t* n_bytes) {
+  return guard([&] {
+    if (!x || !n_bytes || fd < 0) throw pg::Error(PG_EINVAL, "pg_region_vcf_fd: bad arguments");
+    PG_HIP(hipSetDevice(x->c.device));
+    *n_bytes = pg::format_region_vcf(x->c, names, name_off, n_names, nullptr, 0, fd);
+  });
+}
+
 int pg_rows_format(pg_ctx* x, const char* names, const int64_t* name_off, uint64_t n_names, char* out, uint64_t cap,
                    uint64_t* n_bytes) {
   return guard([&] {

@@ -63,6 +63,7 @@
 //
 // Every sum is an integer and every atomic commutes: the result depends on
 // the input alone, whatever the schedule.
+#include "pg_bubbles.h"
 #include "pg_steps.h"
 
 namespace pg {
@@ -79,37 +80,6 @@ namespace pg {
 #define BB_GS_WORDS 32             // presence words a k_vs_groupsum block takes per chunk
 #define BB_NONE (~0ull)            // the segment id of a lane that takes no part
 
-// ------------------------------------------------------------ the tables
-struct BbSites {
-  long long *from, *to;
-  ull *first, *count;
-  uint32_t *nal, *ngen;
-  static size_t bytes(uint64_t n) { return 40 * n + 64; }
-  BbSites(const DevBuf& b, uint64_t n) {
-    from = b.as<long long>();
-    to = from + n;
-    first = reinterpret_cast<ull*>(to + n);
-    count = first + n;
-    nal = reinterpret_cast<uint32_t*>(count + n);
-    ngen = nal + n;
-  }
-};
-// (n + 1 entries per 8-byte column: the scan of regions into ioff takes one more)
-struct BbAlleles {
-  ull *site, *regions, *frow, *count, *lo, *hi, *ioff;
-  uint32_t* ngen;
-  static size_t bytes(uint64_t n) { return 56 * (n + 1) + 4 * n + 64; }
-  BbAlleles(const DevBuf& b, uint64_t n) {
-    site = b.as<ull>();
-    regions = site + n + 1;
-    frow = regions + n + 1;
-    count = frow + n + 1;
-    lo = count + n + 1;
-    hi = lo + n + 1;
-    ioff = hi + n + 1;
-    ngen = reinterpret_cast<uint32_t*>(ioff + n + 1);
-  }
-};
 // the segments' columns (n + 1 entries each), in closing order or sorted
 struct BbSegs {
   ull *ac, *reg, *h1, *h2, *gen, *bp, *frow, *ist;
@@ -274,15 +244,6 @@ __global__ void k_bb_heads(const uint8_t* __restrict__ fl, const ull* __restrict
       apos[na0] = n;
     }
   }
-}
-// the last j in [0, n) with off[j] + step * j <= i (off ascending from 0, off[n] + step * n > i)
-__device__ __forceinline__ uint64_t bb_find(const ull* __restrict__ off, uint64_t n, ull step, ull i) {
-  uint64_t lo = 0, hi = n;
-  while (hi - lo > 1) {
-    const uint64_t mid = lo + (hi - lo) / 2;
-    if (off[mid] + step * mid <= i) lo = mid; else hi = mid;
-  }
-  return lo;
 }
 // ioff[j]: the inner steps of the segments before j.  Inner step i of all: its segment's label against
 // the same position of its group's first segment (equal regions: the position exists there)
@@ -746,6 +707,7 @@ void region_bubbles(Ctx& c, const int64_t* h_rows5, uint64_t n_rows, const int32
   c.bb_groups = G;
   c.bb_words = W;
   c.bb_ready = true;
+  c.vr_ready = false;                                      // (the variants described the old tables)
   if (n_anchors) *n_anchors = nanc;
   if (n_segments) *n_segments = nseg;
   if (n_sites) *n_sites = ns;

@@ -362,6 +362,17 @@ struct Ctx {
   uint32_t bb_groups = 0, bb_words = 0;
   bool bb_ready = false;
   int bb_hash_bits = 0;           // pg_tune: low bits kept of the inner path's hash (0 = all of it)
+  // ---- allele sequences and reference placement (pg_variants.hip): the result of the last pg_region_variants
+  // (a successful pg_region_bubbles clears vr_ready: the texts read the bubbles tables)
+  DevBuf vr_tab;                  // pg_seqdec.h's table: [na] the alleles, then [np] the placed sites' pad + REF
+  DevBuf vr_blob;                 // their letters, every entry's start padded to 16 bytes
+  DevBuf vr_place;                // [np] site, record, pos0, ref row, ref length; uint32 [np] ref allele
+  uint64_t vr_na = 0, vr_np = 0, vr_unplaced = 0, vr_bases = 0;
+  uint64_t vr_pad_al = 0, vr_pad = 0;   // bytes of the padded blob: the alleles' part, all of it
+  bool vr_ready = false;
+  Timer t_vr;                     // the decoder kernel of the last pg_region_variants
+  double ms_vr_decode = 0;
+  uint64_t vr_chunks = 0;         // its 16-letter chunks
 
   // ---- npz persistence (pg_persist.hip)
   DevBuf preload;                 // staged PreEnt pairs, OR-merged by every build
@@ -540,7 +551,8 @@ RowInput row_input(Ctx& c, const char* what, const int64_t* h_rows5, uint64_t n_
                    uint64_t n_records, uint32_t n_groups, bool records_match_always);
 // One pass over the rows (k_row_scan): L = 1 + the largest used label (0: none), the used and the skipped
 // rows, names = 1 + the largest record of a used row.  rf (n + 1 bytes) non-null: the USED / HEAD flag byte
-// of every row, rf[n] = 0.  rec_len non-null: -22 if a used row reaches outside its record.  -34 if L > 2^31.
+// of every row, rf[n] = 0.  rec_len non-null: -22 if a used row reaches outside its record (with or without
+// rf).  -34 if L > 2^31.
 struct RowScan {
   uint64_t L, used, skipped, names;
 };
@@ -640,6 +652,25 @@ uint64_t region_bubbles_inner(Ctx& c, int64_t* inner, uint64_t cap);
 void region_bubbles_groups(Ctx& c, uint64_t* sites, uint64_t* alleles, uint64_t* private_, uint64_t cap);
 void region_bubbles_anchors(Ctx& c, int64_t* label, uint32_t* n_genomes, uint64_t cap);
 uint64_t format_region_bubbles(Ctx& c, char* out, uint64_t cap, int fd = -1);
+
+// pg_variants.hip
+// The bases of every allele of the last region_bubbles and the sites placed on
+// the walks of genome ref_group (UINT32_MAX: none); the rows must be the ones
+// the bubbles were made of.  Replaces the context's previous variants only
+// when it succeeds.
+#define NEED_VARIANTS "no variants (call pg_region_variants first, after the last pg_region_bubbles)"
+void region_variants(Ctx& c, const int64_t* h_rows5, uint64_t n_rows, const int32_t* rec_group, uint64_t n_records,
+                     uint32_t n_groups, uint32_t ref_group, uint64_t* n_alleles, uint64_t* n_bases, uint64_t* n_placed,
+                     uint64_t* n_unplaced);
+void region_variants_alleles(Ctx& c, int64_t* record, int64_t* lo, int64_t* hi, int64_t* strand, uint64_t* len,
+                             uint64_t* gc, uint64_t* amb, uint64_t* offset, uint64_t cap);
+uint64_t region_variants_bases(Ctx& c, uint8_t* out, uint64_t cap);
+void region_variants_placed(Ctx& c, uint64_t* site, int64_t* record, int64_t* pos0, uint64_t* ref_row,
+                            uint32_t* ref_allele, uint64_t* ref_len, uint64_t cap);
+uint64_t format_region_alleles_fasta(Ctx& c, const char* names, const int64_t* name_off, uint64_t n_names, char* out,
+                                     uint64_t cap, int fd = -1);
+uint64_t format_region_vcf(Ctx& c, const char* names, const int64_t* name_off, uint64_t n_names, char* out,
+                           uint64_t cap, int fd = -1);
 
 // helpers
 inline uint64_t next_pow2(uint64_t x) {

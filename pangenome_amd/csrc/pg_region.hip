@@ -162,7 +162,10 @@ RowScan row_scan(Ctx& c, const char* what, const RowInput& in, uint8_t* rf, cons
     DevBuf ctr;
     ctr.reserve(40);
     PG_HIP(hipMemsetAsync(ctr.p, 0, 40, c.stream));
-    if (rf) {
+    if (rf && rec_len) {
+      PG_HIP(hipMemsetAsync(rf + in.n, 0, 1, c.stream));
+      RG_LAUNCH((k_row_scan<true, true>), in.grid_rows, in.rows, in.n, in.group, rf, rec_len, ctr.as<ull>());
+    } else if (rf) {
       PG_HIP(hipMemsetAsync(rf + in.n, 0, 1, c.stream));
       RG_LAUNCH((k_row_scan<true, false>), in.grid_rows, in.rows, in.n, in.group, rf, rec_len, ctr.as<ull>());
     } else if (rec_len) {

@@ -44,38 +44,17 @@
 //      k_rs_copy    the letters, one thread per 16-byte piece of the blob
 //                   (the FASTA and GFA texts and the export without padding)
 //
+// The table (RsTab) and the declarations of k_rs_decode and k_rs_copy are in
+// pg_seqdec.h: pg_variants.hip launches both over a table of its own spans.
+//
 // Bytes (d): 0.25 read and 1 written per base, and 1/16 for e16.
 // Every sum is an integer and every atomic commutes: the result depends on
 // the input alone, whatever the schedule.
-#include "pg_region.h"
+#include "pg_seqdec.h"
 
 namespace pg {
 
 #define RS_ACGT 0x54474341u        // "ACGT", A in the low byte
-#define RS_DECODE_GRID 2048u       // blocks of k_rs_decode and k_rs_copy: past 8 MiB of letters a block loops
-#define RS_NONE (~0ull)
-
-// the table's columns, n + 1 entries each (off[n] and poff[n] are the totals)
-struct RsTab {
-  long long *label, *row, *rec, *start, *end, *strand;
-  ull *len, *gc, *amb, *off, *poff;
-  static size_t bytes(uint64_t n) { return 88 * (n + 1) + 64; }
-  RsTab(const DevBuf& b, uint64_t n) {
-    const uint64_t m = n + 1;
-    label = b.as<long long>();
-    row = label + m;
-    rec = row + m;
-    start = rec + m;
-    end = start + m;
-    strand = end + m;
-    len = reinterpret_cast<ull*>(strand + m);
-    gc = len + m;
-    amb = gc + m;
-    off = amb + m;
-    poff = off + m;
-  }
-};
-
 // ------------------------------------------------------------ b. arg-max
 // d_max[label] = the largest length of its used rows (zeroed before)
 __global__ void __launch_bounds__(RG_BLOCK) k_rs_max(const long long* __restrict__ rows, uint64_t n,
@@ -272,7 +251,8 @@ __global__ void __launch_bounds__(RG_BLOCK) k_rs_decode(PackedCls pc, const long
 }
 
 // ------------------------------------------------------------ e. texts
-// every entry's letters from the blob to dst + dst_off[entry], a 16-byte piece per thread
+// every entry's letters from the blob to dst + dst_off[entry] (RS_NONE: the entry is left out), a 16-byte
+// piece per thread
 struct __attribute__((packed)) RsPiece {
   uint32_t w[4];
 };
@@ -284,7 +264,7 @@ __global__ void __launch_bounds__(RG_BLOCK) k_rs_copy(const uint4* __restrict__ 
   rs_block_range(nchunks, b0, b1);
   for (uint64_t base = b0; base < b1; base += RG_BLOCK) {
     uint64_t q, i;
-    if (!rs_chunk_entry(T.poff, n, base, b1, rng, q, i)) continue;
+    if (!rs_chunk_entry(T.poff, n, base, b1, rng, q, i) || dst_off[i] == RS_NONE) continue;
     const ull j = 16ull * q - T.poff[i], len = T.len[i];
     const uint32_t m = len - j < 16ull ? (uint32_t)(len - j) : 16u;
     const uint4 v = blob[q];

@@ -1193,6 +1193,50 @@ def write_bubbles_files(prefix: str, write_bubbles, table: dict, genome_names, m
     whole("_fr_bubbles.npz", lambda f: np.savez(f, **arrays))
 
 
+VCF_NS = b'##INFO=<ID=NS,Number=1,Type=Integer,Description="Genomes with an allele at the site">\n'
+VCF_GT = (b'##FORMAT=<ID=GT,Number=.,Type=String,Description="Every allele of the site found in the genome, '
+          b'unphased; . if none">\n')
+
+
+def vcf_header(ref_name, contigs, genome_names) -> bytes:
+    """The header of `_fr_variants.vcf`: the file format, the source, the
+    reference genome's name, a contig line per (seqid, length) of contigs -
+    the walked records of that genome - the NS and GT meta lines and the
+    column line with the genome names."""
+    out = [b"##fileformat=VCFv4.2\n", b"##source=pangenome_amd\n", b"##reference=%s\n" % bytes(ref_name)]
+    out += [b"##contig=<ID=%s,length=%d>\n" % (bytes(i), int(n)) for i, n in contigs]
+    out += [VCF_NS, VCF_GT, b"\t".join([b"#CHROM", b"POS", b"ID", b"REF", b"ALT", b"QUAL", b"FILTER", b"INFO",
+                                        b"FORMAT"] + [bytes(x) for x in genome_names]) + b"\n"]
+    return b"".join(out)
+
+
+VARIANT_COLS = ("from", "to", "allele", "regions", "record", "lo", "hi", "strand", "len", "gc", "amb")
+
+
+def write_variants_files(prefix: str, write_fasta, table: dict, ids, header: bytes, write_vcf) -> None:
+    """The three `-V` files of `prefix` (the input's path): `_fr_alleles.fa`
+    (write_fasta(file) writes the text), `_fr_alleles.tsv` from the table's
+    columns (VARIANT_COLS; a record is printed by its seqid, ids[record]) and
+    `_fr_variants.vcf`: header, then the body write_vcf(file) writes; each is
+    written to `.tmp` and renamed when whole."""
+    def whole(suffix, fill):
+        fn = prefix + suffix
+        with open(fn + ".tmp", "wb") as f:
+            fill(f)
+        os.replace(fn + ".tmp", fn)
+    whole("_fr_alleles.fa", write_fasta)
+    cols = [np.asarray(table[k]).tolist() for k in VARIANT_COLS]
+    whole("_fr_alleles.tsv", lambda f: f.write(
+        b"#from\tto\tallele\tregions\tseqid\tstart\tend\tstrand\tlen\tgc\tamb\n" + b"".join(
+            b"%d\t%d\t%d\t%d\t%s\t%d\t%d\t%d\t%d\t%d\t%d\n" % (a, c, k, r, bytes(ids[rec]), lo, hi, st, n, gc, amb)
+            for a, c, k, r, rec, lo, hi, st, n, gc, amb in zip(*cols))))
+
+    def vcf(f):
+        f.write(header)
+        write_vcf(f)
+    whole("_fr_variants.vcf", vcf)
+
+
 def seqid(name: bytes) -> bytes:
     """A record's id: its header without '>' up to the first whitespace."""
     p = bytes(name).split(None, 1)

@@ -9,7 +9,7 @@ runs in libpangenome_hip.so on an MI355X (pangenome_amd/csrc).  Mirrors:
   dbg2rdbg     :1313-1321                rdBG (K5 degree scan + compaction)
   seq2graph    :1853-1951                edges -> .xyz -> mcl -> labels -> rows
   dump / load_on_disk  :243-335         `<in>_db.npz` (oakht slot layout)
-  entry_point  :1971-2146                CLI (-i -k -n -c -r -d -R -D; ours: -a -w -g -p -l -s -v)
+  entry_point  :1971-2146                CLI (-i -k -n -c -r -d -R -D; ours: -a -w -g -p -l -s -v -b -V)
 
 Usage:  python -m pangenome_amd -i genomes.fa -k 27 > result.tab
 """
@@ -257,7 +257,7 @@ def rdbg_edges(g: DeviceGraph, Ns, chunk, rc, brkpt="", keep_on_device=False):
 
 def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_dict=None, saved=None,
               hashfunc=None, jit=True, chunk=2 ** 33, rc=False, cluster=True, out=None, min_weight=1, groups=None,
-              orders=0, links=False, seqs=False, inflation2=3, sites=False, bubbles=0):
+              orders=0, links=False, seqs=False, inflation2=3, sites=False, bubbles=0, variants=""):
     """:1853-1951: edge weights -> `<qry>_rdbg_weight.xyz` -> mcl (or reuse)
     -> label dictionary -> print the region rows.  The edges, the label
     table, the rows and both texts are made on the device; the host writes
@@ -289,7 +289,10 @@ def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_
     written.  bubbles (-b, with groups; 0: off): the variable sites between
     anchor regions - labels carried by that many genomes, at most all of them
     - are made the same way (pg_region_bubbles) and `<qry>_fr_bubbles.tsv`,
-    `_fr_bubbles_genomes.tsv` and `_fr_bubbles.npz` written."""
+    `_fr_bubbles_genomes.tsv` and `_fr_bubbles.npz` written.  variants (-V,
+    with bubbles; "": off): a genome's name; the bases of every allele are
+    decoded and the sites placed on that genome's walks (pg_region_variants),
+    and `<qry>_fr_alleles.fa`, `_fr_alleles.tsv` and `_fr_variants.vcf` written."""
     out = out or sys.stdout
     g = rdbg_dict
     res = rdbg_edges(g, Ns, chunk, rc, brkpt=brkpt, keep_on_device=True)
@@ -368,6 +371,8 @@ def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_
             write_sites(g, qry, names, flags, groups)
         if bubbles:
             write_bubbles(g, qry, names, flags, groups, int(bubbles))
+            if variants:
+                write_variants(g, qry, names, flags, groups, variants)
     gen = g.ctx.label_gen
     return LabelTable(loader=lambda: g.ctx.labels(gen))           # (raises once a later label pass replaced it)
 
@@ -377,10 +382,22 @@ def record_names(g):
     return [bytes(g.buf[int(hs) + 1:int(hs) + int(hl)]) for hs, hl in zip(g.hdr_start, g.hdr_len)]
 
 
-def check_groups(g, Ns, groups):
+def check_groups(g, Ns, groups, variants=""):
     """-g's group file against the records the row pass will walk (raises
-    ValueError for a walked record the file does not name)."""
-    host.assign_groups(record_names(g), host.plan_rows(g.seq_len, g.shape, g.buf, int(Ns)), groups)
+    ValueError for a walked record the file does not name), and -V's name
+    against the genomes (ValueError if it is none of them)."""
+    _, gnames = host.assign_groups(record_names(g), host.plan_rows(g.seq_len, g.shape, g.buf, int(Ns)), groups)
+    if variants:
+        ref_genome(gnames, variants)
+
+
+def ref_genome(gnames, name):
+    """The number of -V's genome: the first genome called `name`."""
+    want = name.encode() if isinstance(name, str) else bytes(name)
+    for i, nm in enumerate(gnames):
+        if bytes(nm) == want:
+            return i
+    raise ValueError("-V: no genome is called %r (%d genomes)" % (want.decode("utf-8", "replace"), len(gnames)))
 
 
 def write_freq(g, qry, names, flags, groups):
@@ -491,6 +508,33 @@ def write_bubbles(g, qry, names, flags, groups, min_genomes):
     host.write_bubbles_files(qry, text, table, gnames, m)
 
 
+def write_variants(g, qry, names, flags, groups, ref_name):
+    """-V: the bubbles just made (write_bubbles) as sequences and against the
+    genome ref_name (pg_region_variants on the device rows, write_freq's
+    genomes) as `<qry>_fr_alleles.fa` and the body of `_fr_variants.vcf` (the
+    device texts; a record is named by its seqid) and `_fr_alleles.tsv`."""
+    rec_group, gnames = host.assign_groups(names, flags, groups)
+    ref = ref_genome(gnames, ref_name)
+    g.ctx.region_variants(rec_group, len(gnames), ref)
+    ids = [host.seqid(x) for x in names]
+    sites, alleles = g.ctx.region_bubbles_table(), g.ctx.region_bubbles_alleles()
+    site = alleles["allele_site"].astype(np.int64)
+    table = g.ctx.region_variants_alleles()
+    table.update({"from": sites["site_from"][site], "to": sites["site_to"][site],
+                  "allele": np.arange(site.shape[0], dtype=np.int64) - sites["site_first"][site].astype(np.int64),
+                  "regions": alleles["allele_regions"]})
+    contigs = [(ids[r], int(g.seq_len[r])) for r in np.flatnonzero(rec_group == ref).tolist()]
+
+    def fasta(f):
+        f.flush()
+        g.ctx.region_alleles_fasta_write(ids, f.fileno())
+
+    def vcf(f):
+        f.flush()
+        g.ctx.region_vcf_write(ids, f.fileno())
+    host.write_variants_files(qry, fasta, table, ids, host.vcf_header(gnames[ref], contigs, gnames), vcf)
+
+
 def _fileno(out):
     """The descriptor under a text stream's binary buffer (stdout, a file),
     or None (a stand-in with no descriptor)."""
@@ -517,6 +561,8 @@ def manual_print(out=None):
                  "      <in>_fr_regions.fa, _fr_regions.tsv and, with -l 1, _fr_graph_seq.gfa (GFA 1 with sequences)",
                  "  -g: frequency table of the regions across genomes. record (each record a genome) or a file of",
                  "      seqid<TAB>genome lines; writes <in>_fr_freq.tsv, _fr_spectrum.tsv, _fr_genomes.tsv, _fr_presence.npz",
+                 "  -V: with -g and -b, this genome as the reference: the alleles of the sites between anchors as sequences, and a VCF",
+                 "      against it. single process only. writes <in>_fr_alleles.fa, _fr_alleles.tsv, _fr_variants.vcf",
                  "  -p: with -g, compare the genomes over this many genome orders (0: off). writes <in>_fr_shared.tsv,",
                  "      _fr_jaccard.tsv (pairs), _fr_curve.tsv (pan and core genome growth), _fr_compare.npz",
                  "  -l: with -g, the graph of the regions along the genomes. 0 (off) or 1; single process only. writes",
@@ -532,7 +578,8 @@ def manual_print(out=None):
 def parse_args(argv):
     """:1983-1997 — same flag handling, including `-k27` and skipped unknowns."""
     args = {"-i": "", "-k": "50", "-n": "2**63", "-r": "", "-d": "", "-R": "", "-D": "", "-c": "2", "-a": "mcl",
-            "-w": "1", "-g": "", "-p": "0", "-l": "0", "-s": "0", "-I": "1.5", "-v": "0", "-b": "0"}
+            "-w": "1", "-g": "", "-p": "0", "-l": "0", "-s": "0", "-I": "1.5", "-v": "0", "-b": "0",
+            "-V": ""}
     N = len(argv)
     for i in range(1, N):
         k = argv[i]
@@ -616,6 +663,14 @@ def bubbles_arg(args):
     return None if b and not args["-g"] else b
 
 
+def variants_arg(args, bubbles):
+    """-V's value: the reference genome's name ("": off), or None when it is
+    refused - given without -g or without -b >= 1."""
+    if not args["-V"]:
+        return ""
+    return args["-V"] if args["-g"] and bubbles else None
+
+
 def entry_point(argv, out=None, device=0):
     out = out or sys.stdout
     args = parse_args(argv)
@@ -623,7 +678,9 @@ def entry_point(argv, out=None, device=0):
     bkt, dbs, rbk, rc, rdb = args["-r"], args["-d"], args["-R"], int(args["-c"]), args["-D"]
     n_orders, links, seqs, sites = compare_orders_arg(args), links_arg(args), seqs_arg(args), sites_arg(args)
     bubbles = bubbles_arg(args)
-    bad = not qry or n_orders is None or links is None or seqs is None or sites is None or bubbles is None
+    variants = variants_arg(args, bubbles)
+    bad = (not qry or n_orders is None or links is None or seqs is None or sites is None or bubbles is None or
+           variants is None)
     clu = None if bad else cluster_args(args)
     if clu is None:
         manual_print(out)
@@ -641,8 +698,10 @@ def entry_point(argv, out=None, device=0):
         clu["sites"] = True
     if bubbles:
         clu["bubbles"] = bubbles
-    # a group file is checked against the records before anything is built
-    chk = (lambda g: check_groups(g, Ns, grp)) if grp and grp != "record" else None
+    if variants:
+        clu["variants"] = variants
+    # a group file, and -V's genome, are checked against the records before anything is built
+    chk = (lambda g: check_groups(g, Ns, grp, variants)) if grp and (grp != "record" or variants) else None
     chunk = 2 ** 33
     rc0, rc1 = (rc >> 1) == 1, (rc & 1) == 1
     if dbs or rdb:                                    # :2073-2101
