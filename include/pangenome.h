@@ -923,6 +923,113 @@ int pg_region_vcf(pg_ctx* ctx, const char* names, const int64_t* name_off, uint6
 int pg_region_vcf_fd(pg_ctx* ctx, const char* names, const int64_t* name_off, uint64_t n_names, int fd,
                      uint64_t* n_bytes);
 
+/* ---- the alleles aligned against their site's reference: CIGARs, the
+ *      primitive differences (SNVs, deletions, insertions) and, for the placed
+ *      sites, the primitives merged into the lines of a VCF.  Integer only; the
+ *      result depends on the input alone, whatever the schedule.
+ * Input: the last successful pg_region_variants and the bubbles result it
+ * belongs to; the pass takes no rows.
+ * Pairs: every site s has a target T.  A placed site's T is the reference
+ * record's own letters [pos0, pos0 + ref_len) - the placed entry's REF without
+ * the padding base - and its skipped allele is ref_allele; every other site's
+ * (PG_NO_REF: every site's) T is the sequence of its allele 0, and 0 is
+ * skipped.  Every other allele of the site is a query Q, in table order; pairs
+ * come by site index, then allele index: n_pairs = n_alleles - n_sites.
+ * Letters compare as bytes (N equals N and nothing else).
+ * Trimming, n = |T|, m = |Q|, the suffix first: q is the largest value <=
+ * min(n, m) for which the last q letters of T and Q are equal, then p the
+ * largest value <= min(n, m) - q for which the first p letters are.  The cores:
+ * t = T[p : n - q] of length a, u = Q[p : m - q] of length b.
+ * Distance: D[i][0] = i, D[0][j] = j, otherwise D[i][j] = min(D[i-1][j-1] +
+ * (t[i-1] != u[j-1]), D[i-1][j] + 1, D[i][j-1] + 1); the distance is D[a][b].
+ * Path, walked from (a, b) to (0, 0).  At (i, j): if i > 0, j > 0 and D[i][j]
+ * == D[i-1][j-1] + (t[i-1] != u[j-1]) the step is diagonal, `=` for equal
+ * letters and `X` otherwise; else if i > 0 and D[i][j] == D[i-1][j] + 1 it is
+ * `D`, a target base with no query base; else `I`.  Going backwards the
+ * diagonal comes first, so a gap sits at the leftmost of its co-optimal
+ * places: AAA against AA deletes the first A.  The choice depends on its cell
+ * alone (the fill stores it in 2 bits; the traceback follows the bits).
+ * CIGAR: the run-length list over all of T and Q: p `=`, the core's runs, q
+ * `=`, runs of length 0 left out; ops `=` `X` `D` `I`; the empty list (n = m =
+ * 0) prints as `*`.  The core's first and last ops are never `=`, and a `D`
+ * run never touches an `I` run.
+ * Size cap: a pair with (a + 1) x (b + 1) above cells_cap (2^24, or
+ * PG_TUNE_ALIGN_CELLS) is not aligned: status 1, CIGAR p `=`, a `D`, b `I`, q
+ * `=`, distance UINT64_MAX (printed `.`), n_del = a, n_ins = b, and one
+ * primitive of type REPL.  Every other pair has status 0.
+ * Pair table, every column uint64: site; allele, the index inside its site;
+ * placed, 0 or 1; t_len, q_len, prefix, suffix; status; distance; n_eq, with
+ * p + q; n_sub, n_ins, n_del, in bases; op_off, n_ops: its runs in the run
+ * arrays - op, one of '=' 'X' 'D' 'I', and len; prim_off, n_prims.
+ * Primitives, per pair in target order: pair, type, tpos, qpos, tlen, qlen,
+ * the offsets into T and Q.  SNV (0): every X column on its own, 1 and 1.  DEL
+ * (1): every maximal D run of length L, L and 0.  INS (2): every maximal I run,
+ * 0 and L; tpos is the target base before which the insertion lies.  REPL (3):
+ * a status 1 pair, tpos = qpos = p, a and b.
+ * Lines: the merged primitives of the placed sites.  Two primitives of one
+ * site are the same line iff (tpos, type, tlen, qlen) are equal and Q[qpos :
+ * qpos + qlen] is, letter by letter.  A line has site; pos, the 1-based VCF
+ * POS: pos0 + tpos + 1 for an SNV, and pos0 + tpos, the anchor base (the
+ * padding base when tpos = 0), for the others; type, tpos, tlen, qlen;
+ * first_prim, the smallest primitive index of the group (its Q gives the ALT
+ * letters); ac, the allele entries that carry it; its carrier set, W =
+ * ceil(n_groups / 64) words, the OR of those alleles' presence bits, and
+ * n_genomes, its popcount.  Lines come by (record, pos, site, type, tlen, qlen,
+ * first_prim) ascending.
+ * Counts (each pointer may be NULL): *n_pairs; *n_aligned, the status 0 pairs;
+ * *n_ops; *n_prims; *n_lines.
+ * PG_EINVAL before any successful pg_region_variants; PG_ENOMEM on an
+ * allocation failure; PG_EDEVICE if two primitives with unequal letters share
+ * every key and their letters' hash (PG_TUNE_ALIGN_HASH_BITS).  In every
+ * refusal the previous result stays.
+ * Device memory while the call runs: per batch of pairs (a + 1) words of 16
+ * choices per core row and b + 1 row values, within PG_TUNE_ALIGN_SCRATCH (256
+ * MiB; one pair if a pair needs more); 5 bytes per run bound, min(a + b, 2
+ * min(a, b) + 1), of every aligned pair; 56 per primitive of a placed site
+ * while the lines are made.  The result: 152 per pair, 9 per run, 41 per
+ * primitive, 85 + 8 W per line and 8 per carrying allele of a line.
+ * Lifetime: a successful pg_region_variants or pg_region_bubbles drops the
+ * result, because it describes theirs; no other pass reads or drops it. */
+int pg_region_align(pg_ctx* ctx, uint64_t* n_pairs, uint64_t* n_aligned, uint64_t* n_ops, uint64_t* n_prims,
+                    uint64_t* n_lines);
+/* The tables of the last pg_region_align; any output pointer may be NULL; cap
+ * (entries) below the table's size is PG_ERANGE.  bits: [n_lines][W].
+ * pg_region_align_time: the fill kernels' time (HIP events, summed over the
+ * batches) and the a x b cells they computed.  All of these and the text
+ * calls below: PG_EINVAL before any pg_region_align. */
+int pg_region_align_pairs(pg_ctx* ctx, uint64_t* site, uint64_t* allele, uint64_t* placed, uint64_t* t_len,
+                          uint64_t* q_len, uint64_t* prefix, uint64_t* suffix, uint64_t* status, uint64_t* distance,
+                          uint64_t* n_eq, uint64_t* n_sub, uint64_t* n_ins, uint64_t* n_del, uint64_t* op_off,
+                          uint64_t* n_ops, uint64_t* prim_off, uint64_t* n_prims, uint64_t cap);
+int pg_region_align_ops(pg_ctx* ctx, uint8_t* op, uint64_t* len, uint64_t cap);
+int pg_region_align_prims(pg_ctx* ctx, uint64_t* pair, uint8_t* type, uint64_t* tpos, uint64_t* qpos, uint64_t* tlen,
+                          uint64_t* qlen, uint64_t cap);
+int pg_region_align_lines(pg_ctx* ctx, uint64_t* site, int64_t* pos, uint8_t* type, uint64_t* tpos, uint64_t* tlen,
+                          uint64_t* qlen, uint64_t* first_prim, uint64_t* ac, uint32_t* n_genomes, uint64_t* bits,
+                          uint64_t cap);
+int pg_region_align_time(pg_ctx* ctx, double* ms_fill, uint64_t* cells);
+/* The pair table's text, formatted on the device: the header
+ * "#from\tto\tallele\ttarget\ttlen\tqlen\tprefix\tsuffix\tdist\teq\tsub\tins\tdel\tcigar\n",
+ * then one line per pair; target is `ref` for a placed site, else `0`; dist is
+ * `.` for a status 1 pair; cigar is <len><op> per run, or `*`.  out, cap,
+ * n_bytes and the _fd form: as pg_region_sites_format and its _fd form. */
+int pg_region_align_format(pg_ctx* ctx, char* out, uint64_t cap, uint64_t* n_bytes);
+int pg_region_align_format_fd(pg_ctx* ctx, int fd, uint64_t* n_bytes);
+/* The primitives' VCF body: one line per line entry, tab separated and newline
+ * ended (no line: empty):
+ *   <names[record]> <pos> <from>_<to> <REF> <ALT> . . NS=<site n_genomes>;AC=<ac> GT <cell g = 0> ... <cell g = G - 1>
+ * SNV: REF is T[tpos] and ALT is Q[qpos].  The others: the anchor letter
+ * (reference base pos - 1, 0-based) followed by T[tpos : tpos + tlen] for REF
+ * and by Q[qpos : qpos + qlen] for ALT.  The cell of genome g: `1` if an allele
+ * of the site with presence bit g carries the line, `0` if an allele of the
+ * site with bit g does not (the reference allele never does), `0/1` if both
+ * hold, `.` if neither does.  The caller writes the header lines.  The
+ * arguments: as pg_region_vcf and pg_region_vcf_fd. */
+int pg_region_primitives_vcf(pg_ctx* ctx, const char* names, const int64_t* name_off, uint64_t n_names, char* out,
+                             uint64_t cap, uint64_t* n_bytes);
+int pg_region_primitives_vcf_fd(pg_ctx* ctx, const char* names, const int64_t* name_off, uint64_t n_names, int fd,
+                                uint64_t* n_bytes);
+
 /* ---- text output (host only; no context).  The reference formats these in
  *      Python loops (kmer_numba.py:1893-1904, :1946-1949).
  * pg_format_xyz: "%d_%d\t%d_%d\t%d\n" per edge (tuples as unsigned).
@@ -1055,6 +1162,20 @@ uint64_t pg_format_rows(const int64_t* rows5, uint64_t n, const char* names, con
  * hash word, so that equal hashes of unequal paths - PG_EDEVICE from the
  * comparison - can be tested.  The results that are returned are the same. */
 #define PG_TUNE_BUBBLE_HASH_BITS 25
+/* PG_TUNE_ALIGN_CELLS: pg_region_align's cells_cap: a pair whose (a + 1) x
+ * (b + 1) is above it is not aligned (status 1).  1 .. 2^30 (the fill counts
+ * in 32 bits); 0 (default) = 2^24. */
+#define PG_TUNE_ALIGN_CELLS 26
+/* PG_TUNE_ALIGN_SCRATCH: bytes of direction bits and row values one batch of
+ * pg_region_align's pairs may take.  0 (default) = 256 MiB; a value below one
+ * pair's need gives one pair per batch.  The same results at any value. */
+#define PG_TUNE_ALIGN_SCRATCH 27
+/* PG_TUNE_ALIGN_HASH_BITS: pg_region_align groups the primitives of a site by
+ * a hash of their query letters before it compares them letter by letter.  0
+ * (default) = the full hash; 1..64 = only that many low bits, so that equal
+ * hashes of unequal letters - PG_EDEVICE from the comparison - can be tested.
+ * The results that are returned are the same. */
+#define PG_TUNE_ALIGN_HASH_BITS 28
 int pg_tune(pg_ctx* ctx, int what, int64_t value);
 
 /* Device bytes the library's buffers hold in this process now (peak == 0)

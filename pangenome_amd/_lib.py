@@ -40,6 +40,9 @@ PG_TUNE_CMP_CHUNK = 22          # pg_freq_compare's shared pass: label-axis word
 PG_TUNE_CMP_FORM = 23           # pg_freq_compare's curve pass: 0 LDS counters up to 2048 genomes, 1 global atomics
 PG_TUNE_RDBG_KEYS = 24          # 0 the range pass counts rdBG members, keys swept from the table on export; 1 keys written by the build
 PG_TUNE_BUBBLE_HASH_BITS = 25   # 0 the full hash of an inner path; 1..32 its low bits only (tests of the comparison)
+PG_TUNE_ALIGN_CELLS = 26        # pg_region_align: a pair with more cells than this is not aligned (0 = 2^24)
+PG_TUNE_ALIGN_SCRATCH = 27      # pg_region_align: bytes of direction bits per batch of pairs (0 = 256 MiB)
+PG_TUNE_ALIGN_HASH_BITS = 28    # 0 the full hash of a primitive's letters; 1..64 its low bits only (tests of the comparison)
 
 
 class PgStats(C.Structure):
@@ -157,6 +160,16 @@ SIGNATURES = {
     "pg_region_alleles_fasta_fd": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, _U64P]),
     "pg_region_vcf": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint64, _U64P]),
     "pg_region_vcf_fd": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, _U64P]),
+    "pg_region_align": (C.c_int, [_P, _U64P, _U64P, _U64P, _U64P, _U64P]),
+    "pg_region_align_pairs": (C.c_int, [_P] + [_P] * 17 + [C.c_uint64]),
+    "pg_region_align_ops": (C.c_int, [_P, _P, _P, C.c_uint64]),
+    "pg_region_align_prims": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_uint64]),
+    "pg_region_align_lines": (C.c_int, [_P] + [_P] * 10 + [C.c_uint64]),
+    "pg_region_align_time": (C.c_int, [_P, C.POINTER(C.c_double), _U64P]),
+    "pg_region_align_format": (C.c_int, [_P, _P, C.c_uint64, _U64P]),
+    "pg_region_align_format_fd": (C.c_int, [_P, C.c_int, _U64P]),
+    "pg_region_primitives_vcf": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint64, _U64P]),
+    "pg_region_primitives_vcf_fd": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, _U64P]),
     "pg_rows_format": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint64, _U64P]),
     "pg_rows_format_fd": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_int, _U64P]),
     "pg_get_stats": (C.c_int, [_P, _SP]),
@@ -1155,6 +1168,85 @@ class Context:
         """region_vcf_text(names) written straight to descriptor fd at its
         position (pg_region_vcf_fd); flush any buffered writer on fd first."""
         return _write(self.h, self.lib.pg_region_vcf_fd, "pg_region_vcf_fd", fd, *_names_args(names))
+
+    ALIGN_PAIR_COLS = ("site", "allele", "placed", "t_len", "q_len", "prefix", "suffix", "status", "distance", "n_eq",
+                       "n_sub", "n_ins", "n_del", "op_off", "n_ops", "prim_off", "n_prims")
+
+    def region_align(self):
+        """Every allele of the last region_variants() aligned against its
+        site's reference - a placed site's REF, else the site's allele 0
+        (pg_region_align).  Returns (n_pairs, n_aligned, n_ops, n_prims,
+        n_lines); the result stays on the device (region_align_pairs / _ops /
+        _prims / _lines, region_align_text, region_primitives_vcf_text and
+        their _write forms) until the next region_variants() or
+        region_bubbles()."""
+        out = [C.c_uint64() for _ in range(5)]
+        check(self.lib.pg_region_align(self.h, *[C.byref(x) for x in out]), "pg_region_align")
+        self.n_align = tuple(x.value for x in out)
+        return self.n_align
+
+    def region_align_pairs(self) -> dict:
+        """The pair table, every column uint64: ALIGN_PAIR_COLS (pg_region_align_pairs)."""
+        n = getattr(self, "n_align", (0,) * 5)[0]
+        t = {k: np.empty(n, np.uint64) for k in self.ALIGN_PAIR_COLS}
+        check(self.lib.pg_region_align_pairs(self.h, *[ptr(a) for a in t.values()], n), "pg_region_align_pairs")
+        return t
+
+    def region_align_ops(self) -> dict:
+        """The runs of every pair one after another: op (uint8, one of
+        b"=XDI") and len (uint64) (pg_region_align_ops)."""
+        n = getattr(self, "n_align", (0,) * 5)[2]
+        t = {"op": np.empty(n, np.uint8), "len": np.empty(n, np.uint64)}
+        check(self.lib.pg_region_align_ops(self.h, ptr(t["op"]), ptr(t["len"]), n), "pg_region_align_ops")
+        return t
+
+    def region_align_prims(self) -> dict:
+        """The primitives: pair, type (uint8: 0 SNV, 1 DEL, 2 INS, 3 REPL),
+        tpos, qpos, tlen, qlen (pg_region_align_prims)."""
+        n = getattr(self, "n_align", (0,) * 5)[3]
+        t = {k: np.empty(n, np.uint8 if k == "type" else np.uint64)
+             for k in ("pair", "type", "tpos", "qpos", "tlen", "qlen")}
+        check(self.lib.pg_region_align_prims(self.h, *[ptr(a) for a in t.values()], n), "pg_region_align_prims")
+        return t
+
+    def region_align_lines(self, n_groups: int) -> dict:
+        """The merged lines of the placed sites in the VCF's order: site, pos
+        (int64), type (uint8), tpos, tlen, qlen, first_prim, ac, n_genomes
+        (uint32) and bits, uint64 [lines, ceil(n_groups / 64)] (pg_region_align_lines)."""
+        n = getattr(self, "n_align", (0,) * 5)[4]
+        t = {k: np.empty(n, np.uint64) for k in ("site", "pos", "type", "tpos", "tlen", "qlen", "first_prim", "ac")}
+        t["pos"], t["type"] = np.empty(n, np.int64), np.empty(n, np.uint8)
+        t["n_genomes"] = np.empty(n, np.uint32)
+        t["bits"] = np.empty((n, (int(n_groups) + 63) // 64), np.uint64)
+        check(self.lib.pg_region_align_lines(self.h, *[ptr(a) for a in t.values()], n), "pg_region_align_lines")
+        return t
+
+    def region_align_time(self):
+        """(ms, cells): the fill kernels' time in the last region_align() and
+        the cells they computed (pg_region_align_time)."""
+        ms, n = C.c_double(), C.c_uint64()
+        check(self.lib.pg_region_align_time(self.h, C.byref(ms), C.byref(n)), "pg_region_align_time")
+        return ms.value, n.value
+
+    def region_align_text(self) -> bytes:
+        """The pair table's text, formatted on the device (pg_region_align_format)."""
+        return _text(self.h, self.lib.pg_region_align_format, "pg_region_align_format")
+
+    def region_align_write(self, fd: int) -> int:
+        """region_align_text() written straight to descriptor fd at its
+        position (pg_region_align_format_fd); flush any buffered writer on fd first."""
+        return _write(self.h, self.lib.pg_region_align_format_fd, "pg_region_align_format_fd", fd)
+
+    def region_primitives_vcf_text(self, names: list) -> bytes:
+        """The primitives' VCF body, one line per merged primitive, formatted
+        on the device (pg_region_primitives_vcf); names[r] = record r's name."""
+        return _text(self.h, self.lib.pg_region_primitives_vcf, "pg_region_primitives_vcf", *_names_args(names))
+
+    def region_primitives_vcf_write(self, names: list, fd: int) -> int:
+        """region_primitives_vcf_text(names) written straight to descriptor fd
+        at its position (pg_region_primitives_vcf_fd); flush any buffered writer on fd first."""
+        return _write(self.h, self.lib.pg_region_primitives_vcf_fd, "pg_region_primitives_vcf_fd", fd,
+                      *_names_args(names))
 
     def rows_export(self, n: int):
         """The [n, 5] rows of the last rows_count() (pg_rows_export)."""

@@ -405,6 +405,19 @@ int pg_tune(pg_ctx* x, int what, int64_t value) {
         if (value < 0 || value > 32) throw pg::Error(PG_EINVAL, "pg_tune: bubble hash bits must be in [0, 32]");
         x->c.bb_hash_bits = (int)value;
         break;
+      case PG_TUNE_ALIGN_CELLS:
+        if (value < 0 || value > (1ll << 30))
+          throw pg::Error(PG_EINVAL, "pg_tune: alignment cells cap must be in [0, 2^30]");
+        x->c.al_cells_cap = (uint64_t)value;
+        break;
+      case PG_TUNE_ALIGN_SCRATCH:
+        if (value < 0) throw pg::Error(PG_EINVAL, "pg_tune: alignment scratch bytes must be >= 0");
+        x->c.al_scratch = (uint64_t)value;
+        break;
+      case PG_TUNE_ALIGN_HASH_BITS:
+        if (value < 0 || value > 64) throw pg::Error(PG_EINVAL, "pg_tune: alignment hash bits must be in [0, 64]");
+        x->c.al_hash_bits = (int)value;
+        break;
       case PG_TUNE_STAGE_SLOTS:
         if (value < 0 || value == 1 || value > 8) throw pg::Error(PG_EINVAL, "pg_tune: staging slots must be 0 or 2..8");
         x->c.stage_slots = value ? (uint64_t)value : 4;
@@ -1218,6 +1231,98 @@ int pg_region_vcf_fd(pg_ctx* x, const char* names, const int64_t* name_off, uint
     if (!x || !n_bytes || fd < 0) throw pg::Error(PG_EINVAL, "pg_region_vcf_fd: bad arguments");
     PG_HIP(hipSetDevice(x->c.device));
     *n_bytes = pg::format_region_vcf(x->c, names, name_off, n_names, nullptr, 0, fd);
+  });
+}
+
+int pg_region_align(pg_ctx* x, uint64_t* n_pairs, uint64_t* n_aligned, uint64_t* n_ops, uint64_t* n_prims,
+                    uint64_t* n_lines) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_region_align: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::region_align(x->c, n_pairs, n_aligned, n_ops, n_prims, n_lines);
+  });
+}
+
+int pg_region_align_pairs(pg_ctx* x, uint64_t* site, uint64_t* allele, uint64_t* placed, uint64_t* t_len,
+                          uint64_t* q_len, uint64_t* prefix, uint64_t* suffix, uint64_t* status, uint64_t* distance,
+                          uint64_t* n_eq, uint64_t* n_sub, uint64_t* n_ins, uint64_t* n_del, uint64_t* op_off,
+                          uint64_t* n_ops, uint64_t* prim_off, uint64_t* n_prims, uint64_t cap) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_region_align_pairs: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    uint64_t* const cols[17] = {site, allele, placed, t_len, q_len, prefix, suffix, status, distance,
+                                n_eq, n_sub,  n_ins,  n_del, op_off, n_ops, prim_off, n_prims};
+    pg::region_align_pairs(x->c, cols, cap);
+  });
+}
+
+int pg_region_align_ops(pg_ctx* x, uint8_t* op, uint64_t* len, uint64_t cap) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_region_align_ops: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::region_align_ops(x->c, op, len, cap);
+  });
+}
+
+int pg_region_align_prims(pg_ctx* x, uint64_t* pair, uint8_t* type, uint64_t* tpos, uint64_t* qpos, uint64_t* tlen,
+                          uint64_t* qlen, uint64_t cap) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_region_align_prims: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::region_align_prims(x->c, pair, type, tpos, qpos, tlen, qlen, cap);
+  });
+}
+
+int pg_region_align_lines(pg_ctx* x, uint64_t* site, int64_t* pos, uint8_t* type, uint64_t* tpos, uint64_t* tlen,
+                          uint64_t* qlen, uint64_t* first_prim, uint64_t* ac, uint32_t* n_genomes, uint64_t* bits,
+                          uint64_t cap) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_region_align_lines: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::region_align_lines(x->c, site, pos, type, tpos, tlen, qlen, first_prim, ac, n_genomes, bits, cap);
+  });
+}
+
+int pg_region_align_time(pg_ctx* x, double* ms_fill, uint64_t* cells) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_region_align_time: ctx is NULL");
+    if (!x->c.al_ready) throw pg::Error(PG_EINVAL, std::string("pg_region_align_time: ") + NEED_ALIGN);
+    if (ms_fill) *ms_fill = x->c.ms_al_fill;
+    if (cells) *cells = x->c.al_cells;
+  });
+}
+
+int pg_region_align_format(pg_ctx* x, char* out, uint64_t cap, uint64_t* n_bytes) {
+  return guard([&] {
+    if (!x || !n_bytes) throw pg::Error(PG_EINVAL, "pg_region_align_format: bad arguments");
+    PG_HIP(hipSetDevice(x->c.device));
+    *n_bytes = pg::format_region_align(x->c, out, cap);
+  });
+}
+
+int pg_region_align_format_fd(pg_ctx* x, int fd, uint64_t* n_bytes) {
+  return guard([&] {
+    if (!x || !n_bytes || fd < 0) throw pg::Error(PG_EINVAL, "pg_region_align_format_fd: bad arguments");
+    PG_HIP(hipSetDevice(x->c.device));
+    *n_bytes = pg::format_region_align(x->c, nullptr, 0, fd);
+  });
+}
+
+int pg_region_primitives_vcf(pg_ctx* x, const char* names, const int64_t* name_off, uint64_t n_names, char* out,
+                             uint64_t cap, uint64_t* n_bytes) {
+  return guard([&] {
+    if (!x || !n_bytes) throw pg::Error(PG_EINVAL, "pg_region_primitives_vcf: bad arguments");
+    PG_HIP(hipSetDevice(x->c.device));
+    *n_bytes = pg::format_region_primitives_vcf(x->c, names, name_off, n_names, out, cap);
+  });
+}
+
+int pg_region_primitives_vcf_fd(pg_ctx* x, const char* names, const int64_t* name_off, uint64_t n_names, int fd,
+                                uint64_t* n_bytes) {
+  return guard([&] {
+    if (!x || !n_bytes || fd < 0) throw pg::Error(PG_EINVAL, "pg_region_primitives_vcf_fd: bad arguments");
+    PG_HIP(hipSetDevice(x->c.device));
+    *n_bytes = pg::format_region_primitives_vcf(x->c, names, name_off, n_names, nullptr, 0, fd);
   });
 }
 

@@ -708,6 +708,7 @@ void region_bubbles(Ctx& c, const int64_t* h_rows5, uint64_t n_rows, const int32
   c.bb_words = W;
   c.bb_ready = true;
   c.vr_ready = false;                                      // (the variants described the old tables)
+  c.al_ready = false;                                      // (and so did their alignments)
   if (n_anchors) *n_anchors = nanc;
   if (n_segments) *n_segments = nseg;
   if (n_sites) *n_sites = ns;

@@ -373,6 +373,21 @@ struct Ctx {
   Timer t_vr;                     // the decoder kernel of the last pg_region_variants
   double ms_vr_decode = 0;
   uint64_t vr_chunks = 0;         // its 16-letter chunks
+  // ---- allele alignments (pg_align.hip): the result of the last pg_region_align (a successful
+  // pg_region_variants or pg_region_bubbles clears al_ready: it describes their tables)
+  DevBuf al_pairs;                // [n + 1] x 19 columns (AlPairs)
+  DevBuf al_ops;                  // [n] len; uint8 [n] op
+  DevBuf al_prims;                // [n + 1] pair, tpos, qpos, tlen, qlen; uint8 [n] type
+  DevBuf al_lines;                // [n + 1] x 10 columns (AlLines); uint32 [n] genomes; uint8 [n] type
+  DevBuf al_bits;                 // [lines][W] carrier words
+  DevBuf al_memb;                 // the alleles that carry the lines, a line's one after another
+  uint64_t al_np = 0, al_aligned = 0, al_nops = 0, al_nprims = 0, al_nl = 0, al_cells = 0;
+  double ms_al_fill = 0;
+  bool al_ready = false;
+  Timer t_al;                     // the fill kernels of the last pg_region_align, batch by batch
+  uint64_t al_cells_cap = 0;      // pg_tune: cells above which a pair is not aligned (0 = 2^24)
+  uint64_t al_scratch = 0;        // pg_tune: bytes of direction bits per batch (0 = 256 MiB)
+  int al_hash_bits = 0;           // pg_tune: low bits kept of a primitive's letters' hash (0 = all of it)
 
   // ---- npz persistence (pg_persist.hip)
   DevBuf preload;                 // staged PreEnt pairs, OR-merged by every build
@@ -671,6 +686,25 @@ uint64_t format_region_alleles_fasta(Ctx& c, const char* names, const int64_t* n
                                      uint64_t cap, int fd = -1);
 uint64_t format_region_vcf(Ctx& c, const char* names, const int64_t* name_off, uint64_t n_names, char* out,
                            uint64_t cap, int fd = -1);
+
+// pg_align.hip
+// Every allele of the last region_variants aligned against its site's
+// reference (the placed site's REF, else allele 0): CIGARs, primitives and
+// the merged lines of the placed sites.  Replaces the context's previous
+// alignments only when it succeeds.
+#define NEED_ALIGN "no alignments (call pg_region_align first, after the last pg_region_variants)"
+void region_align(Ctx& c, uint64_t* n_pairs, uint64_t* n_aligned, uint64_t* n_ops, uint64_t* n_prims,
+                  uint64_t* n_lines);
+void region_align_pairs(Ctx& c, uint64_t* const cols[17], uint64_t cap);
+void region_align_ops(Ctx& c, uint8_t* op, uint64_t* len, uint64_t cap);
+void region_align_prims(Ctx& c, uint64_t* pair, uint8_t* type, uint64_t* tpos, uint64_t* qpos, uint64_t* tlen,
+                        uint64_t* qlen, uint64_t cap);
+void region_align_lines(Ctx& c, uint64_t* site, int64_t* pos, uint8_t* type, uint64_t* tpos, uint64_t* tlen,
+                        uint64_t* qlen, uint64_t* first_prim, uint64_t* ac, uint32_t* n_genomes, uint64_t* bits,
+                        uint64_t cap);
+uint64_t format_region_align(Ctx& c, char* out, uint64_t cap, int fd = -1);
+uint64_t format_region_primitives_vcf(Ctx& c, const char* names, const int64_t* name_off, uint64_t n_names, char* out,
+                                      uint64_t cap, int fd = -1);
 
 // helpers
 inline uint64_t next_pow2(uint64_t x) {

@@ -8,7 +8,8 @@
 //                (zero before) are counted.  Reads rec, start, end, strand,
 //                len and poff; n entries, nchunks = poff[n] / 16.
 //   k_rs_copy    every entry's letters from the blob to dst + dst_off[entry]
-// Their arguments are described at the definitions.
+// Their arguments are described at the definitions.  pg_variants.hip's placed
+// table is laid out here as well, for the pass that reads it (pg_align.hip).
 #pragma once
 #include "pg_region.h"
 
@@ -35,6 +36,22 @@ struct RsTab {
     amb = gc + m;
     off = amb + m;
     poff = off + m;
+  }
+};
+
+// pg_variants.hip's placed table (c.vr_place, n entries), which pg_align.hip reads too
+struct VrPlaced {
+  ull *site, *row, *len;
+  long long *rec, *pos;
+  uint32_t* refal;
+  static size_t bytes(uint64_t n) { return 44 * n + 64; }
+  VrPlaced(const DevBuf& b, uint64_t n) {
+    site = b.as<ull>();
+    row = site + n;
+    len = row + n;
+    rec = reinterpret_cast<long long*>(len + n);
+    pos = rec + n;
+    refal = reinterpret_cast<uint32_t*>(pos + n);
   }
 };
 

@@ -64,22 +64,6 @@ namespace pg {
 #define VR_BAD_NOREF 8ull          //   a reference segment matches no allele
 #define VR_NONE32 0xFFFFFFFFu
 
-// the placed table's columns (n entries)
-struct VrPlaced {
-  ull *site, *row, *len;
-  long long *rec, *pos;
-  uint32_t* refal;
-  static size_t bytes(uint64_t n) { return 44 * n + 64; }
-  VrPlaced(const DevBuf& b, uint64_t n) {
-    site = b.as<ull>();
-    row = site + n;
-    len = row + n;
-    rec = reinterpret_cast<long long*>(len + n);
-    pos = rec + n;
-    refal = reinterpret_cast<uint32_t*>(pos + n);
-  }
-};
-
 __device__ __forceinline__ long long vr_lo(const long long* q) { return q[1] < q[2] ? q[1] : q[2]; }
 __device__ __forceinline__ long long vr_hi(const long long* q) { return q[1] < q[2] ? q[2] : q[1]; }
 // row j goes on the run of the row before it
@@ -489,6 +473,7 @@ void region_variants(Ctx& c, const int64_t* h_rows5, uint64_t n_rows, const int3
   c.vr_pad_al = pad_al;
   c.vr_pad = pad;
   c.vr_ready = true;
+  c.al_ready = false;                                      // (the alignments described the old alleles)
   if (n_alleles) *n_alleles = na;
   if (n_bases) *n_bases = bases;
   if (n_placed) *n_placed = np;

@@ -1210,6 +1210,35 @@ def vcf_header(ref_name, contigs, genome_names) -> bytes:
     return b"".join(out)
 
 
+VCF_AC = b'##INFO=<ID=AC,Number=1,Type=Integer,Description="Alleles of the site that carry the difference">\n'
+VCF_GT_PRIM = (b'##FORMAT=<ID=GT,Number=.,Type=String,Description="1: an allele of the site in the genome carries the '
+               b'difference, 0: one does not, 0/1: both, unphased; . if the genome has no allele">\n')
+
+
+def primitives_vcf_header(ref_name, contigs, genome_names) -> bytes:
+    """The header of `_fr_primitives.vcf`: vcf_header's lines with an AC meta
+    line after NS and the GT description of a line per difference."""
+    return vcf_header(ref_name, contigs, genome_names).replace(VCF_GT, VCF_AC + VCF_GT_PRIM)
+
+
+def write_align_files(prefix: str, write_tsv, header: bytes, write_vcf) -> None:
+    """The two `-A` files of `prefix` (the input's path): `_fr_align.tsv`
+    (write_tsv(file) writes the text) and `_fr_primitives.vcf`: header, then
+    the body write_vcf(file) writes; each is written to `.tmp` and renamed
+    when whole."""
+    def whole(suffix, fill):
+        fn = prefix + suffix
+        with open(fn + ".tmp", "wb") as f:
+            fill(f)
+        os.replace(fn + ".tmp", fn)
+    whole("_fr_align.tsv", write_tsv)
+
+    def vcf(f):
+        f.write(header)
+        write_vcf(f)
+    whole("_fr_primitives.vcf", vcf)
+
+
 VARIANT_COLS = ("from", "to", "allele", "regions", "record", "lo", "hi", "strand", "len", "gc", "amb")
 
 

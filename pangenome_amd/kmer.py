@@ -257,7 +257,7 @@ def rdbg_edges(g: DeviceGraph, Ns, chunk, rc, brkpt="", keep_on_device=False):
 
 def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_dict=None, saved=None,
               hashfunc=None, jit=True, chunk=2 ** 33, rc=False, cluster=True, out=None, min_weight=1, groups=None,
-              orders=0, links=False, seqs=False, inflation2=3, sites=False, bubbles=0, variants=""):
+              orders=0, links=False, seqs=False, inflation2=3, sites=False, bubbles=0, variants="", align=False):
     """:1853-1951: edge weights -> `<qry>_rdbg_weight.xyz` -> mcl (or reuse)
     -> label dictionary -> print the region rows.  The edges, the label
     table, the rows and both texts are made on the device; the host writes
@@ -292,7 +292,10 @@ def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_
     `_fr_bubbles_genomes.tsv` and `_fr_bubbles.npz` written.  variants (-V,
     with bubbles; "": off): a genome's name; the bases of every allele are
     decoded and the sites placed on that genome's walks (pg_region_variants),
-    and `<qry>_fr_alleles.fa`, `_fr_alleles.tsv` and `_fr_variants.vcf` written."""
+    and `<qry>_fr_alleles.fa`, `_fr_alleles.tsv` and `_fr_variants.vcf` written.
+    align (-A, with variants): every allele is then aligned against its
+    site's reference on the device (pg_region_align) and `<qry>_fr_align.tsv`
+    and `_fr_primitives.vcf` written."""
     out = out or sys.stdout
     g = rdbg_dict
     res = rdbg_edges(g, Ns, chunk, rc, brkpt=brkpt, keep_on_device=True)
@@ -373,6 +376,8 @@ def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_
             write_bubbles(g, qry, names, flags, groups, int(bubbles))
             if variants:
                 write_variants(g, qry, names, flags, groups, variants)
+                if align:
+                    write_align(g, qry, names, flags, groups, variants)
     gen = g.ctx.label_gen
     return LabelTable(loader=lambda: g.ctx.labels(gen))           # (raises once a later label pass replaced it)
 
@@ -535,6 +540,27 @@ def write_variants(g, qry, names, flags, groups, ref_name):
     host.write_variants_files(qry, fasta, table, ids, host.vcf_header(gnames[ref], contigs, gnames), vcf)
 
 
+def write_align(g, qry, names, flags, groups, ref_name):
+    """-A: the alleles just decoded (write_variants) aligned against their
+    site's reference (pg_region_align) as `<qry>_fr_align.tsv` and the body
+    of `_fr_primitives.vcf` (the device texts; a record is named by its
+    seqid), behind write_variants' header with an AC line."""
+    rec_group, gnames = host.assign_groups(names, flags, groups)
+    ref = ref_genome(gnames, ref_name)
+    g.ctx.region_align()
+    ids = [host.seqid(x) for x in names]
+    contigs = [(ids[r], int(g.seq_len[r])) for r in np.flatnonzero(rec_group == ref).tolist()]
+
+    def tsv(f):
+        f.flush()
+        g.ctx.region_align_write(f.fileno())
+
+    def vcf(f):
+        f.flush()
+        g.ctx.region_primitives_vcf_write(ids, f.fileno())
+    host.write_align_files(qry, tsv, host.primitives_vcf_header(gnames[ref], contigs, gnames), vcf)
+
+
 def _fileno(out):
     """The descriptor under a text stream's binary buffer (stdout, a file),
     or None (a stand-in with no descriptor)."""
@@ -549,6 +575,8 @@ def manual_print(out=None):
     out = out or sys.stdout
     for line in ("Usage:", "  pyhton this.py -i qry.fsa -k 10 -n 1000000", "Parameters:",
                  "  -i: query sequences in fasta format", "  -k: kmer length",
+                 "  -A: with -V, every allele aligned against the reference: CIGARs, and the SNVs and indels one per VCF line. 0 (off)",
+                 "      or 1; single process only. writes <in>_fr_align.tsv, _fr_primitives.vcf",
                  "  -d: the de bruijn graph", "  -r: break point of de bruijn graph",
                  "  -D: the reduced de bruijn graph", "  -R: break point of reduced de bruijn graph",
                  "  -v: with -g, the variable sites: pairs of regions joined in two or more ways, directly or through one region.",
@@ -579,7 +607,7 @@ def parse_args(argv):
     """:1983-1997 — same flag handling, including `-k27` and skipped unknowns."""
     args = {"-i": "", "-k": "50", "-n": "2**63", "-r": "", "-d": "", "-R": "", "-D": "", "-c": "2", "-a": "mcl",
             "-w": "1", "-g": "", "-p": "0", "-l": "0", "-s": "0", "-I": "1.5", "-v": "0", "-b": "0",
-            "-V": ""}
+            "-V": "", "-A": "0"}
     N = len(argv)
     for i in range(1, N):
         k = argv[i]
@@ -671,6 +699,14 @@ def variants_arg(args, bubbles):
     return args["-V"] if args["-g"] and bubbles else None
 
 
+def align_arg(args, variants):
+    """-A's value: False (0) or True (1), or None for a value that is refused
+    - anything else, or 1 without an accepted -V."""
+    if args["-A"] not in ("0", "1"):
+        return None
+    return None if args["-A"] == "1" and not variants else args["-A"] == "1"
+
+
 def entry_point(argv, out=None, device=0):
     out = out or sys.stdout
     args = parse_args(argv)
@@ -679,8 +715,9 @@ def entry_point(argv, out=None, device=0):
     n_orders, links, seqs, sites = compare_orders_arg(args), links_arg(args), seqs_arg(args), sites_arg(args)
     bubbles = bubbles_arg(args)
     variants = variants_arg(args, bubbles)
+    align = align_arg(args, variants)
     bad = (not qry or n_orders is None or links is None or seqs is None or sites is None or bubbles is None or
-           variants is None)
+           variants is None or align is None)
     clu = None if bad else cluster_args(args)
     if clu is None:
         manual_print(out)
@@ -700,6 +737,8 @@ def entry_point(argv, out=None, device=0):
         clu["bubbles"] = bubbles
     if variants:
         clu["variants"] = variants
+    if align:
+        clu["align"] = True
     # a group file, and -V's genome, are checked against the records before anything is built
     chk = (lambda g: check_groups(g, Ns, grp, variants)) if grp and (grp != "record" or variants) else None
     chunk = 2 ** 33
