@@ -22,13 +22,12 @@ from align_util import (INS, REPL, SNV, assert_files, check_align, check_propert
                         reference_align, runs_of, summary)
 from freq_util import fasta_names, rows5_of, rows_of
 from golden_util import Fixture
+from pangenome_rows_util import BORDERS, other, site_frame
 from seq_util import fasta_records, make_fasta, parse
 from test_align_host import BREAK, HAND, HAND_TAIL, mutate, seg, site_records
 from variants_util import reference_variants
 
 pytestmark = pytest.mark.gpu
-
-BORDERS = (0, 1, 2, 15, 16, 17, 63, 64, 65, 127, 128, 129)
 
 
 @pytest.fixture(scope="module")
@@ -47,10 +46,6 @@ def km():
 
 def acgt(n, seed):
     return bytes(np.frombuffer(b"ACGT", np.uint8)[np.random.default_rng(seed).integers(0, 4, n)])
-
-
-def other(ch):
-    return b"ACGT"[(b"ACGT".index(ch) + 1) % 4]
 
 
 def run(c, sites, ref_group, G=2, min_genomes=2, **kw):
@@ -93,29 +88,17 @@ def test_hand_cases(ctx, T, Q, cigar, prims, vcf):
 
 # ------------------------------------------------------------ 3. strip and word borders
 def border_site(shift, seed=11):
-    """One site: a 200-letter target, and for every (a, b) of BORDERS x BORDERS
-    a query that shares the target's first `shift` + 16 x letters, replaces the
-    next a by b others - about 5 % edits of them, or unrelated letters, by
-    turns - whose ends differ from the replaced ones', and shares the rest."""
+    """pangenome_rows_util.site_frame's site with a 200-letter target of
+    uniform noise, the cores about 5 % edits of the letters they replace, or
+    unrelated letters, by turns."""
     rng = np.random.default_rng(seed + shift)
-    T = acgt(200, 300 + shift)
-    alleles, k = [(T, 0, 1)], 0
-    for a in BORDERS:
-        for b in BORDERS:
-            p = shift + 16 * (k % 3)
-            t = T[p:p + a]
-            if k % 2 and a and b:
-                u = bytearray(mutate(rng, t, 0.05)[:b])
-                u += bytes(rng.choice(list(b"ACGT"), b - len(u)).astype(np.uint8))
-            else:
-                u = bytearray(acgt(b, 1000 * shift + k))
-            if a and b:
-                u[0], u[-1] = (other(t[0]), other(t[-1])) if b > 1 else (other(t[0]),) * 2
-                if b == 1 and a > 1 and u[0] == t[-1]:
-                    u[0] = next(x for x in b"ACGT" if x not in (t[0], t[-1]))
-            alleles.append((T[:p] + bytes(u) + T[p + a:], 1 + k % 2, 1 if k % 3 else -1))
-            k += 1
-    return [alleles]
+
+    def core(k, t, b):
+        if k % 2 and t and b:
+            u = mutate(rng, t, 0.05)[:b]
+            return u + bytes(rng.choice(list(b"ACGT"), b - len(u)).astype(np.uint8))
+        return acgt(b, 1000 * shift + k)
+    return site_frame(acgt(200, 300 + shift), shift, core)
 
 
 @pytest.mark.parametrize("shift", range(16))
