@@ -957,6 +957,28 @@ int pg_region_vcf_fd(pg_ctx* ctx, const char* names, const int64_t* name_off, ui
  * PG_TUNE_ALIGN_CELLS) is not aligned: status 1, CIGAR p `=`, a `D`, b `I`, q
  * `=`, distance UINT64_MAX (printed `.`), n_del = a, n_ins = b, and one
  * primitive of type REPL.  Every other pair has status 0.
+ * Band form (PG_TUNE_ALIGN_BAND 1; nothing of this at 0): only the pairs above
+ * cells_cap change, and no table or text marks them.  One with a == 0 or b ==
+ * 0 is aligned without a fill: status 0, b `I` or a `D`, distance a + b, one
+ * INS or DEL.  Any other is tried at the thresholds t_k = t0 2^k (t0 = 64, or
+ * PG_TUNE_ALIGN_BAND_T0), a band of band_cells(t) = a x min(b, 2 t + 1) cells.
+ * k_lo is the smallest k with t_k >= |a - b|, k* the smallest with t_k >=
+ * D[a][b], k_hi the largest with band_cells(t_k) <= band_cap (2^26, or
+ * PG_TUNE_ALIGN_BAND_CELLS), -1 if there is none.  The pair is aligned iff k*
+ * <= k_hi: status 0, and every column, run and primitive is what the
+ * definition above gives over the full D, as at an unlimited cells_cap;
+ * otherwise it keeps status 1 as above.  Its attempts: max(0, min(k*, k_hi) -
+ * k_lo + 1).  A pair with a + b >= 2^30 is never tried (the fill counts in 32
+ * bits).
+ * Why a band is exact: the band fill takes only the cells with |j - i| <= t and
+ * counts every other neighbour as infinity; its values B are >= D.  A cheapest
+ * path to a cell with D[i][j] <= t passes only cells (i', j') with |j' - i'|
+ * <= D[i'][j'] <= t, all in the band, so B = D there: B[a][b] <= t iff D[a][b]
+ * <= t.  Then every cell of the path has D <= t, and each test of the path
+ * rule gives with B what it gives with D: if D[i][j] == D[i-1][j-1] + ne, that
+ * neighbour has D <= t and is exact in B; if it holds in B, D[i-1][j-1] + ne
+ * <= B[i-1][j-1] + ne = D[i][j], and the recurrence says >=.  The same for
+ * the other two neighbours.
  * Pair table, every column uint64: site; allele, the index inside its site;
  * placed, 0 or 1; t_len, q_len, prefix, suffix; status; distance; n_eq, with
  * p + q; n_sub, n_ins, n_del, in bases; op_off, n_ops: its runs in the run
@@ -984,8 +1006,11 @@ int pg_region_vcf_fd(pg_ctx* ctx, const char* names, const int64_t* name_off, ui
  * refusal the previous result stays.
  * Device memory while the call runs: per batch of pairs (a + 1) words of 16
  * choices per core row and b + 1 row values, within PG_TUNE_ALIGN_SCRATCH (256
- * MiB; one pair if a pair needs more); 5 bytes per run bound, min(a + b, 2
- * min(a, b) + 1), of every aligned pair; 56 per primitive of a placed site
+ * MiB; one pair if a pair needs more) - in the band form at threshold t, a
+ * pair takes a ceil(min(b, 2 min(t, max(a, b)) + 79) / 16) + b + 1 words, every
+ * 64-row strip's choices from its first column less one, rounded down to a
+ * multiple of 16; 5 bytes per run bound, min(a + b, 2 min(a, b) + 1), of every
+ * aligned pair and every pair the band form tries; 56 per primitive of a placed site
  * while the lines are made.  The result: 152 per pair, 9 per run, 41 per
  * primitive, 85 + 8 W per line and 8 per carrying allele of a line.
  * Lifetime: a successful pg_region_variants or pg_region_bubbles drops the
@@ -1008,6 +1033,14 @@ int pg_region_align_lines(pg_ctx* ctx, uint64_t* site, int64_t* pos, uint8_t* ty
                           uint64_t* qlen, uint64_t* first_prim, uint64_t* ac, uint32_t* n_genomes, uint64_t* bits,
                           uint64_t cap);
 int pg_region_align_time(pg_ctx* ctx, double* ms_fill, uint64_t* cells);
+/* The band form's part of the last pg_region_align (every pointer may be
+ * NULL; all 0 with PG_TUNE_ALIGN_BAND 0): *n_over, the pairs above cells_cap;
+ * *n_banded, those of them that came out aligned (the ones with an empty core
+ * side included); *n_attempts, the attempts summed; *band_cells, band_cells(t_k)
+ * summed over the attempts; *ms_band, the band fills' time (HIP events), which
+ * pg_region_align_time leaves out.  PG_EINVAL before any pg_region_align. */
+int pg_region_align_band(pg_ctx* ctx, uint64_t* n_over, uint64_t* n_banded, uint64_t* n_attempts, uint64_t* band_cells,
+                         double* ms_band);
 /* The pair table's text, formatted on the device: the header
  * "#from\tto\tallele\ttarget\ttlen\tqlen\tprefix\tsuffix\tdist\teq\tsub\tins\tdel\tcigar\n",
  * then one line per pair; target is `ref` for a placed site, else `0`; dist is
@@ -1176,6 +1209,17 @@ uint64_t pg_format_rows(const int64_t* rows5, uint64_t n, const char* names, con
  * hashes of unequal letters - PG_EDEVICE from the comparison - can be tested.
  * The results that are returned are the same. */
 #define PG_TUNE_ALIGN_HASH_BITS 28
+/* PG_TUNE_ALIGN_BAND: 0 (default) = pg_region_align gives up every pair above
+ * cells_cap; 1 = it aligns them in a band of diagonals (pg_region_align's
+ * "Band form").  Nothing else changes. */
+#define PG_TUNE_ALIGN_BAND 29
+/* PG_TUNE_ALIGN_BAND_CELLS: the band form's band_cap: a pair is given up
+ * before a band of more cells.  1 .. 2^34; 0 (default) = 2^26. */
+#define PG_TUNE_ALIGN_BAND_CELLS 30
+/* PG_TUNE_ALIGN_BAND_T0: the band form's first threshold t0.  1 .. 2^20; 0
+ * (default) = 64.  For tests: at 1 the band's edges and the doubling show on
+ * cores of a few dozen letters. */
+#define PG_TUNE_ALIGN_BAND_T0 31
 int pg_tune(pg_ctx* ctx, int what, int64_t value);
 
 /* Device bytes the library's buffers hold in this process now (peak == 0)

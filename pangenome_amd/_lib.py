@@ -43,6 +43,9 @@ PG_TUNE_BUBBLE_HASH_BITS = 25   # 0 the full hash of an inner path; 1..32 its lo
 PG_TUNE_ALIGN_CELLS = 26        # pg_region_align: a pair with more cells than this is not aligned (0 = 2^24)
 PG_TUNE_ALIGN_SCRATCH = 27      # pg_region_align: bytes of direction bits per batch of pairs (0 = 256 MiB)
 PG_TUNE_ALIGN_HASH_BITS = 28    # 0 the full hash of a primitive's letters; 1..64 its low bits only (tests of the comparison)
+PG_TUNE_ALIGN_BAND = 29         # pg_region_align: 1 = the pairs above the cells cap are aligned in a band of diagonals
+PG_TUNE_ALIGN_BAND_CELLS = 30   # the band form: a pair is given up before a band of more cells than this (0 = 2^26)
+PG_TUNE_ALIGN_BAND_T0 = 31      # the band form: the first threshold, doubled until it holds the distance (0 = 64)
 
 
 class PgStats(C.Structure):
@@ -166,6 +169,7 @@ SIGNATURES = {
     "pg_region_align_prims": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_uint64]),
     "pg_region_align_lines": (C.c_int, [_P] + [_P] * 10 + [C.c_uint64]),
     "pg_region_align_time": (C.c_int, [_P, C.POINTER(C.c_double), _U64P]),
+    "pg_region_align_band": (C.c_int, [_P, _U64P, _U64P, _U64P, _U64P, C.POINTER(C.c_double)]),
     "pg_region_align_format": (C.c_int, [_P, _P, C.c_uint64, _U64P]),
     "pg_region_align_format_fd": (C.c_int, [_P, C.c_int, _U64P]),
     "pg_region_primitives_vcf": (C.c_int, [_P, _P, _P, C.c_uint64, _P, C.c_uint64, _U64P]),
@@ -1227,6 +1231,15 @@ class Context:
         ms, n = C.c_double(), C.c_uint64()
         check(self.lib.pg_region_align_time(self.h, C.byref(ms), C.byref(n)), "pg_region_align_time")
         return ms.value, n.value
+
+    def region_align_band(self):
+        """(n_over, n_banded, n_attempts, band_cells, ms): the band form's part
+        of the last region_align() - the pairs above the cells cap, those of
+        them that came out aligned, the attempts, their band cells and the band
+        fills' time; zeros with PG_TUNE_ALIGN_BAND 0 (pg_region_align_band)."""
+        out, ms = [C.c_uint64() for _ in range(4)], C.c_double()
+        check(self.lib.pg_region_align_band(self.h, *[C.byref(x) for x in out], C.byref(ms)), "pg_region_align_band")
+        return tuple(x.value for x in out) + (ms.value,)
 
     def region_align_text(self) -> bytes:
         """The pair table's text, formatted on the device (pg_region_align_format)."""

@@ -418,6 +418,20 @@ int pg_tune(pg_ctx* x, int what, int64_t value) {
         if (value < 0 || value > 64) throw pg::Error(PG_EINVAL, "pg_tune: alignment hash bits must be in [0, 64]");
         x->c.al_hash_bits = (int)value;
         break;
+      case PG_TUNE_ALIGN_BAND:
+        if (value < 0 || value > 1) throw pg::Error(PG_EINVAL, "pg_tune: alignment band must be 0 or 1");
+        x->c.al_band = (int)value;
+        break;
+      case PG_TUNE_ALIGN_BAND_CELLS:
+        if (value < 0 || value > (1ll << 34))
+          throw pg::Error(PG_EINVAL, "pg_tune: alignment band cells cap must be in [0, 2^34]");
+        x->c.al_band_cap = (uint64_t)value;
+        break;
+      case PG_TUNE_ALIGN_BAND_T0:
+        if (value < 0 || value > (1ll << 20))
+          throw pg::Error(PG_EINVAL, "pg_tune: alignment band first threshold must be in [0, 2^20]");
+        x->c.al_band_t0 = (uint64_t)value;
+        break;
       case PG_TUNE_STAGE_SLOTS:
         if (value < 0 || value == 1 || value > 8) throw pg::Error(PG_EINVAL, "pg_tune: staging slots must be 0 or 2..8");
         x->c.stage_slots = value ? (uint64_t)value : 4;
@@ -1289,6 +1303,19 @@ int pg_region_align_time(pg_ctx* x, double* ms_fill, uint64_t* cells) {
     if (!x->c.al_ready) throw pg::Error(PG_EINVAL, std::string("pg_region_align_time: ") + NEED_ALIGN);
     if (ms_fill) *ms_fill = x->c.ms_al_fill;
     if (cells) *cells = x->c.al_cells;
+  });
+}
+
+int pg_region_align_band(pg_ctx* x, uint64_t* n_over, uint64_t* n_banded, uint64_t* n_attempts, uint64_t* band_cells,
+                         double* ms_band) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_region_align_band: ctx is NULL");
+    if (!x->c.al_ready) throw pg::Error(PG_EINVAL, std::string("pg_region_align_band: ") + NEED_ALIGN);
+    if (n_over) *n_over = x->c.al_nover;
+    if (n_banded) *n_banded = x->c.al_nbanded;
+    if (n_attempts) *n_attempts = x->c.al_nattempts;
+    if (band_cells) *band_cells = x->c.al_bandcells;
+    if (ms_band) *ms_band = x->c.ms_al_band;
   });
 }
 

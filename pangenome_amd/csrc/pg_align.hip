@@ -30,6 +30,11 @@
 //   e. k_al_trace   one lane per pair follows the bits from (a, b) and writes
 //                   its runs backwards into the pair's bound; the sums come
 //                   from the same walk, and D[a][b] of the fill must equal them
+//   d'. PG_TUNE_ALIGN_BAND: the pairs above the cap, in rounds at the thresholds t0,
+//      2 t0, 4 t0, ...: k_al_fill_band is k_al_fill over the cells with |j - i|
+//      <= t alone, a strip's column window instead of its whole rows, and the
+//      walk back (k_al_trace<true>) takes a pair whose D[a][b] is within t -
+//      exactly what the whole matrix gives - and leaves the others to 2 t
 //   f. k_al_count, two scans, k_al_emit: the exact run and primitive arrays
 //   g. lines: the placed sites' primitives selected, their letters hashed,
 //      stable radix sorts by (site, tpos, type, tlen, qlen, hash), boundary
@@ -57,6 +62,8 @@ namespace pg {
 #define AL_DEL 1u
 #define AL_INS 2u
 #define AL_REPL 3u
+#define AL_INF (1 << 30)           // a cell outside the band: it never wins, and + 1 does not overflow
+#define AL_BAND_MOST (1ull << 30)  // a + b of a band candidate stays below it: every value inside the band is below AL_INF
 
 // the pair table's columns, n + 1 entries each (the scans take one more); the first 17 are exported
 // (toff, qoff: where T and Q start in the blob)
@@ -130,9 +137,10 @@ __global__ void k_al_pairs(BbSites T, BbAlleles A, RsTab V, VrPlaced P, const ul
 
 // ------------------------------------------------------------ b. trimming
 // need[j]: the 32-bit words pair j's fill takes (0: no fill - not aligned, or an empty core);
-// bound[j]: the most runs its core can have; cells[j]: a x b if it is filled
+// bound[j]: the most runs its core can have; cells[j]: a x b if it is filled.  band: a pair above the cap with
+// an empty core side is aligned as it stands, and one with two sides (a candidate of the band form) gets its bound
 __global__ void __launch_bounds__(RG_BLOCK) k_al_trim(const char* __restrict__ blob, AlPairs R, uint64_t n, ull cap,
-                                                      ull* __restrict__ need, ull* __restrict__ bound,
+                                                      int band, ull* __restrict__ need, ull* __restrict__ bound,
                                                       ull* __restrict__ cells) {
   const unsigned l = threadIdx.x & 63u;
   for (uint64_t j = blockIdx.x * (uint64_t)AL_WAVES + (threadIdx.x >> 6); j < n; j += (uint64_t)gridDim.x * AL_WAVES) {
@@ -161,14 +169,14 @@ __global__ void __launch_bounds__(RG_BLOCK) k_al_trim(const char* __restrict__ b
     if (l == 0) {
       const ull a = nn - p - q, b = m - p - q;
       const bool over = a + 1ull > cap / (b + 1ull);       // (a + 1)(b + 1) > cap, without the product
-      const bool core = !over && a && b;
+      const bool core = !over && a && b, cand = band && over && a && b && a + b < AL_BAND_MOST;
       R.prefix[j] = p;
       R.suffix[j] = q;
-      R.status[j] = over;
+      R.status[j] = over && !(band && (!a || !b));
       need[j] = core ? a * ((b + 15ull) >> 4) + b + 1ull : 0ull;
       cells[j] = core ? a * b : 0ull;
       const ull mn = a < b ? a : b;
-      bound[j] = core ? (a + b < 2ull * mn + 1ull ? a + b : 2ull * mn + 1ull) : 0ull;
+      bound[j] = core || cand ? (a + b < 2ull * mn + 1ull ? a + b : 2ull * mn + 1ull) : 0ull;
     }
   }
 }
@@ -248,22 +256,138 @@ __global__ void __launch_bounds__(RG_BLOCK) k_al_fill(const char* __restrict__ b
   }
 }
 
+// ------------------------------------------------------------ d'. the fill in a band
+// The geometry of a band fill of an a x b core at threshold tt.  t: the threshold, no wider than the matrix.
+// The choices of row i, strip st = (i - 1) / 64, lie in W words from bit column start(st) on: the strip's first
+// column less one, max(0, 64 st - t), rounded down to a multiple of 16 - its last is below 64 st + 64 + t, so
+// W = ceil(min(b, 2 t + 79) / 16) serves every strip.  A pair takes a W + b + 1 words.
+struct AlBand {
+  ull t, W;
+  __host__ __device__ AlBand(ull a, ull b, ull tt) {
+    const ull mx = a > b ? a : b;
+    t = tt < mx ? tt : mx;
+    const ull w = 2ull * t + 79ull;
+    W = ((w < b ? w : b) + 15ull) >> 4;
+  }
+  __host__ __device__ ull start(ull st) const { return 64ull * st > t ? (64ull * st - t) & ~15ull : 0ull; }
+  __host__ __device__ ull words(ull a, ull b) const { return a * W + b + 1ull; }
+};
+
+// k_al_fill over the cells with |j - i| <= t alone.  Strip st starts at column w0 = start(st): lane l computes
+// column w0 + s - l at step s, if it lies in its row's part of the band, steps s0 .. s1.  Whatever lies outside
+// the band is AL_INF made here, never read: a lane's value while it computes nothing (so the left of a row's
+// first column and the up of its last one, one column right of the row above's), lane 0's up values from the
+// row buffer outside row 64 st's part, and the border D[i][0] below row t.  Only the band's part of lane 63's
+// row is written back.
+__global__ void __launch_bounds__(RG_BLOCK) k_al_fill_band(const char* __restrict__ blob, AlPairs R,
+                                                           const ull* __restrict__ order, const ull* __restrict__ moff,
+                                                           uint64_t nb, ull tt, uint32_t* __restrict__ scratch,
+                                                           ull* __restrict__ fdist) {
+  const int l = (int)(threadIdx.x & 63u);
+  const uint64_t w = blockIdx.x * (uint64_t)AL_WAVES + (threadIdx.x >> 6);
+  if (w >= nb) return;                                     // (a whole wave)
+  const ull j = order[w], p = R.prefix[j];
+  const int a = (int)(R.tlen[j] - p - R.suffix[j]), b = (int)(R.qlen[j] - p - R.suffix[j]);
+  const unsigned char* t = reinterpret_cast<const unsigned char*>(blob) + R.toff[j] + p;
+  const unsigned char* u = reinterpret_cast<const unsigned char*>(blob) + R.qoff[j] + p;
+  const AlBand B((ull)a, (ull)b, tt);
+  const int th = (int)B.t;
+  const size_t stride = (size_t)B.W;
+  uint32_t* M = scratch + moff[w];
+  int* row = reinterpret_cast<int*>(M + (size_t)a * stride);
+  for (int st = 0; st * 64 < a; ++st) {
+    const int r = st * 64, i = r + l + 1, w0 = (int)B.start((ull)st);
+    const bool mine = i <= a, leave = r + 64 <= a;         // lane 63 has a row: the next strip reads it
+    const int last = leave ? r + 64 : a;                   // the strip's last row and its last column
+    const int chi = b - last <= th ? b : last + th;
+    const int steps = (chi - w0 + last - r + 63) & ~63;    // that row's last step + 1, rounded up to whole loads
+    const int jlo = i - th > 1 ? i - th : 1, jhi = b - i <= th ? b : i + th;
+    const int s0 = mine ? jlo - w0 + l : 1, s1 = mine ? jhi - w0 + l : 0;
+    const int tc = mine ? (int)t[i - 1] : 0;
+    uint32_t* Mi = M + (size_t)(mine ? i - 1 : 0) * stride;
+    int cur = AL_INF, diag = AL_INF, qc = 0, rb = AL_INF, uq = 0, wb = 0;
+    uint32_t bits = 0;
+    for (int s = 0; s < steps; ++s) {
+      if ((s & 63) == 0) {                                 // lane 0's next 64 letters and up values
+        const int c = w0 + s + l;
+        const bool in = c >= 1 && c <= b;
+        uq = in ? (int)u[c - 1] : 0;
+        rb = in && c - r <= th && r - c <= th ? (st ? row[c] : c) : AL_INF;
+      }
+      int up = __shfl_up(cur, 1), uc = __shfl_up(qc, 1);
+      const int up0 = __builtin_amdgcn_readlane(rb, s & 63), uc0 = __builtin_amdgcn_readlane(uq, s & 63);
+      if (l == 0) {
+        up = up0;
+        uc = uc0;
+      }
+      qc = uc;
+      int now = AL_INF;
+      if (s >= s0 && s <= s1) {
+        const int x = s - l - 1, jj = w0 + x + 1;          // bit column x of the strip's window
+        const int left = jj == 1 ? (i <= th ? i : AL_INF) : cur, dg = jj == 1 ? i - 1 : diag;
+        const int ne = tc != uc;
+        const int d0 = dg + ne, d1 = up + 1, d2 = left + 1;
+        uint32_t code;
+        if (d0 <= d1 && d0 <= d2) {
+          code = (uint32_t)ne;
+          now = d0;
+        } else if (d1 <= d2) {
+          code = 2u;
+          now = d1;
+        } else {
+          code = 3u;
+          now = d2;
+        }
+        const int cb = x & 15;
+        bits |= code << (2 * cb);
+        if (cb == 15 || s == s1) {
+          Mi[x >> 4] = bits;
+          bits = 0;
+        }
+        if (i == a && jj == b) fdist[j] = (ull)now;
+      }
+      cur = now;
+      diag = up;
+      const int c63 = __builtin_amdgcn_readlane(cur, 63);  // lane 63 after step s: column w0 + s - 63
+      if (l == (s & 63)) wb = c63;
+      if ((s & 63) == 63 && leave) {
+        const int col = w0 + s - 126 + l;
+        if (col >= 1 && col <= b && col - last <= th && last - col <= th) row[col] = wb;
+      }
+    }
+    __threadfence_block();                                 // the row is in memory before the next strip loads it
+  }
+}
+
 // ------------------------------------------------------------ e. the traceback
-// the runs of pair j's core, in target order, end at rop / rlen [roff[j] + bound[j]); nrun[j] of them
+// the runs of pair j's core, in target order, end at rop / rlen [roff[j] + bound[j]); nrun[j] of them.
+// BAND: the bits lie as k_al_fill_band left them at threshold tt.  A pair whose D[a][b] is above it is left
+// alone, done[w] = 0; any other is exact, and the walk stays inside the band: the pair gets status 0 and
+// need[j] = 1 (steps f to h then read its runs), done[w] = 1
+template <bool BAND>
 __global__ void k_al_trace(AlPairs R, const ull* __restrict__ order, const ull* __restrict__ moff, uint64_t nb,
                            const uint32_t* __restrict__ scratch, const ull* __restrict__ roff,
                            const ull* __restrict__ bound, uint8_t* __restrict__ rop, uint32_t* __restrict__ rlen,
-                           ull* __restrict__ nrun, const ull* __restrict__ fdist, ull* bad) {
+                           ull* __restrict__ nrun, const ull* __restrict__ fdist, ull* bad, ull tt,
+                           ull* __restrict__ need, ull* __restrict__ done) {
   RG_LOOP(w, nb) {
     const ull j = order[w], p = R.prefix[j];
-    const ull a = R.tlen[j] - p - R.suffix[j], b = R.qlen[j] - p - R.suffix[j], stride = (b + 15ull) >> 4;
+    const ull a = R.tlen[j] - p - R.suffix[j], b = R.qlen[j] - p - R.suffix[j];
+    const AlBand B(a, b, tt);
+    const ull stride = BAND ? B.W : (b + 15ull) >> 4;
+    if (BAND) {
+      done[w] = fdist[j] <= B.t;
+      if (fdist[j] > B.t) continue;
+    }
     const uint32_t* M = scratch + moff[w];
     const ull lo = roff[j];
     ull at = lo + bound[j], i = a, jj = b, runs = 0, eq = 0, sub = 0, del = 0, ins = 0, gaps = 0;
     uint32_t op = 4, len = 0;
-    bool full = false;
+    bool full = false, astray = false;
     while (i || jj) {
-      const uint32_t code = i && jj ? (M[(i - 1ull) * stride + ((jj - 1ull) >> 4)] >> (2u * ((jj - 1ull) & 15ull))) & 3u
+      const ull x = jj - 1ull, w0 = BAND ? B.start((i - 1ull) >> 6) : 0ull;
+      if (BAND && i && jj && (x < w0 || (x - w0) >> 4 >= stride)) { astray = true; break; }
+      const uint32_t code = i && jj ? (M[(i - 1ull) * stride + ((x - w0) >> 4)] >> (2u * (x & 15ull))) & 3u
                                     : (i ? 2u : 3u);
       if (code != op) {
         if (len) {
@@ -296,7 +420,11 @@ __global__ void k_al_trace(AlPairs R, const ull* __restrict__ order, const ull* 
       }
     }
     if (full) RG_OR(bad, AL_BAD_BOUND);
-    if (sub + del + ins != fdist[j]) RG_OR(bad, AL_BAD_DIST);
+    if (astray || sub + del + ins != fdist[j]) RG_OR(bad, AL_BAD_DIST);
+    if (BAND) {
+      R.status[j] = 0;
+      need[j] = 1;
+    }
     nrun[j] = runs;
     R.neq[j] = eq;
     R.nsub[j] = sub;
@@ -599,6 +727,7 @@ void region_align(Ctx& c, uint64_t* n_pairs, uint64_t* n_aligned, uint64_t* n_op
   const uint32_t W = c.bb_words;
   const ull cells_cap = c.al_cells_cap ? c.al_cells_cap : 1ull << 24;
   const uint64_t budget = (c.al_scratch ? c.al_scratch : 256ull << 20) / 4;   // in words
+  const ull band_cap = c.al_band_cap ? c.al_band_cap : 1ull << 26, band_t0 = c.al_band_t0 ? c.al_band_t0 : 64ull;
   const BbSites T(c.bb_sites, ns);
   const BbAlleles A(c.bb_alleles, na);
   const RsTab V(c.vr_tab, na + np);
@@ -608,9 +737,9 @@ void region_align(Ctx& c, uint64_t* n_pairs, uint64_t* n_aligned, uint64_t* n_op
 
   // ---- everything is built aside; the context's result is replaced at the end
   DevBuf pairs, ops, prims, lines, lbits, memb, bad, pl, needw, bound, cellw, roff, nrun, fdist, rop, rlen, scratch, dord,
-      dmoff;
-  uint64_t aligned = 0, nops = 0, nprims = 0, nl = 0, cells = 0;
-  double ms = 0;
+      dmoff, bdone;
+  uint64_t aligned = 0, nops = 0, nprims = 0, nl = 0, cells = 0, nover = 0, nbanded = 0, nattempts = 0, bandcells = 0;
+  double ms = 0, msband = 0;
   pairs.reserve(AlPairs::bytes(n));
   bad.reserve(16);
   PG_HIP(hipMemsetAsync(bad.p, 0, 8, c.stream));
@@ -627,7 +756,7 @@ void region_align(Ctx& c, uint64_t* n_pairs, uint64_t* n_aligned, uint64_t* n_op
     fdist.reserve(8 * (n + 1));
     RG_LAUNCH(k_al_pairs, grid_for(na, RG_BLOCK, 8192), T, A, V, P, pl.as<ull>(), na, R);
     cellw.reserve(8 * (n + 1));
-    RG_LAUNCH(k_al_trim, grid_for(n, AL_WAVES, 8192), blob, R, n, cells_cap, needw.as<ull>(), bound.as<ull>(),
+    RG_LAUNCH(k_al_trim, grid_for(n, AL_WAVES, 8192), blob, R, n, cells_cap, c.al_band, needw.as<ull>(), bound.as<ull>(),
               cellw.as<ull>());
     const uint64_t nbound = excl_scan_total(c, bound.as<ull>(), roff.as<ull>(), n);
     rop.reserve(nbound + 16);
@@ -646,20 +775,27 @@ void region_align(Ctx& c, uint64_t* n_pairs, uint64_t* n_aligned, uint64_t* n_op
     }
     std::stable_sort(order.begin(), order.end(), [&](ull x, ull y) { return hneed[x] > hneed[y]; });
     const uint64_t nf = order.size();
-    std::vector<ull> moff(nf);
-    std::vector<uint64_t> cut{0};                          // batch b = order[cut[b] .. cut[b + 1])
-    uint64_t most = 0, used = 0;
-    for (uint64_t k = 0; k < nf; ++k) {
-      // (a batch is one grid of k_al_fill: a wave per pair and no loop)
-      if (used && (used + hneed[order[k]] > budget || k - cut.back() >= 65536ull * AL_WAVES)) {
-        cut.push_back(k);
-        used = 0;
+    std::vector<ull> moff;
+    std::vector<uint64_t> cut;                             // batch b = order[cut[b] .. cut[b + 1])
+    // words[k]: what the k-th pair of a list takes; its place in its batch's scratch, the cuts, the largest batch
+    auto batches = [&](auto&& words, uint64_t count) {
+      moff.assign(count, 0);
+      cut.assign(1, 0);
+      uint64_t most = 0, used = 0;
+      for (uint64_t k = 0; k < count; ++k) {
+        // (a batch is one grid of a fill: a wave per pair and no loop)
+        if (used && (used + words(k) > budget || k - cut.back() >= 65536ull * AL_WAVES)) {
+          cut.push_back(k);
+          used = 0;
+        }
+        moff[k] = used;
+        used += words(k);
+        most = std::max(most, used);
       }
-      moff[k] = used;
-      used += hneed[order[k]];
-      most = std::max(most, used);
-    }
-    cut.push_back(nf);
+      cut.push_back(count);
+      return most;
+    };
+    const uint64_t most = batches([&](uint64_t k) { return hneed[order[k]]; }, nf);
     if (nf) {
       scratch.reserve(4 * most + 16);
       dord.reserve(8 * nf);
@@ -675,11 +811,88 @@ void region_align(Ctx& c, uint64_t* n_pairs, uint64_t* n_aligned, uint64_t* n_op
       RG_LAUNCH(k_al_fill, grid_for(nb, AL_WAVES), blob, R, dord.as<ull>() + k0, dmoff.as<ull>() + k0, nb,
                 scratch.as<uint32_t>(), fdist.as<ull>());
       c.t_al.stop(c.stream);
-      RG_LAUNCH(k_al_trace, grid_for(nb, RG_BLOCK, 8192), R, dord.as<ull>() + k0, dmoff.as<ull>() + k0, nb,
+      RG_LAUNCH(k_al_trace<false>, grid_for(nb, RG_BLOCK, 8192), R, dord.as<ull>() + k0, dmoff.as<ull>() + k0, nb,
                 scratch.as<uint32_t>(), roff.as<ull>(), bound.as<ull>(), rop.as<uint8_t>(), rlen.as<uint32_t>(),
-                nrun.as<ull>(), fdist.as<ull>(), bad.as<ull>());
+                nrun.as<ull>(), fdist.as<ull>(), bad.as<ull>(), 0ull, nullptr, nullptr);
       c.sync();
       ms += c.t_al.ms();
+    }
+    // ---- d'. the band form: the pairs above the cap with two core sides, round k at the threshold t0 2^k.  A
+    // pair joins at the first threshold that holds |a - b|, leaves aligned once D[a][b] is within the threshold,
+    // and leaves as it is (status 1) when the next band would take more than band_cap cells
+    if (c.al_band) {
+      struct Cand { ull j, a, b; uint64_t k; };
+      std::vector<Cand> alive, round;
+      std::vector<ull> ht(n), hq(n), hp(n), hs(n), hdone;
+      PG_HIP(hipMemcpyAsync(ht.data(), R.tlen, 8 * n, hipMemcpyDeviceToHost, c.stream));
+      PG_HIP(hipMemcpyAsync(hq.data(), R.qlen, 8 * n, hipMemcpyDeviceToHost, c.stream));
+      PG_HIP(hipMemcpyAsync(hp.data(), R.prefix, 8 * n, hipMemcpyDeviceToHost, c.stream));
+      PG_HIP(hipMemcpyAsync(hs.data(), R.suffix, 8 * n, hipMemcpyDeviceToHost, c.stream));
+      c.sync();
+      auto bcells = [](const Cand& x, ull t) { return x.a * std::min(x.b, 2ull * t + 1ull); };
+      for (uint64_t j = 0; j < n; ++j) {
+        const ull a = ht[j] - hp[j] - hs[j], b = hq[j] - hp[j] - hs[j];
+        if (a + 1ull <= cells_cap / (b + 1ull)) continue;
+        ++nover;
+        if (!a || !b) {                                    // (k_al_trim gave it status 0: counted as aligned above)
+          ++nbanded;
+          continue;
+        }
+        Cand x{j, a, b, 0};
+        while (band_t0 << x.k < (a > b ? a - b : b - a)) ++x.k;
+        if (a + b < AL_BAND_MOST && bcells(x, band_t0 << x.k) <= band_cap) alive.push_back(x);
+      }
+      if (!alive.empty()) c.t_al.init();
+      for (uint64_t k = 0; !alive.empty(); ++k) {
+        const ull t = band_t0 << k;
+        round.clear();
+        for (const Cand& x : alive)
+          if (x.k <= k) round.push_back(x);
+        const uint64_t nr = round.size();
+        if (!nr) continue;
+        auto words = [&](const Cand& x) { return AlBand(x.a, x.b, t).words(x.a, x.b); };
+        std::stable_sort(round.begin(), round.end(), [&](const Cand& x, const Cand& y) { return words(x) > words(y); });
+        const uint64_t top = batches([&](uint64_t i) { return words(round[i]); }, nr);
+        std::vector<ull> ord(nr);
+        for (uint64_t i = 0; i < nr; ++i) ord[i] = round[i].j;
+        scratch.reserve(4 * top + 16);
+        dord.reserve(8 * nr);
+        dmoff.reserve(8 * nr);
+        bdone.reserve(8 * nr);
+        PG_HIP(hipMemcpyAsync(dord.p, ord.data(), 8 * nr, hipMemcpyHostToDevice, c.stream));
+        PG_HIP(hipMemcpyAsync(dmoff.p, moff.data(), 8 * nr, hipMemcpyHostToDevice, c.stream));
+        for (size_t bt = 0; bt + 1 < cut.size(); ++bt) {
+          const uint64_t k0 = cut[bt], nb = cut[bt + 1] - k0;
+          c.t_al.start(c.stream);
+          RG_LAUNCH(k_al_fill_band, grid_for(nb, AL_WAVES), blob, R, dord.as<ull>() + k0, dmoff.as<ull>() + k0, nb, t,
+                    scratch.as<uint32_t>(), fdist.as<ull>());
+          c.t_al.stop(c.stream);
+          RG_LAUNCH(k_al_trace<true>, grid_for(nb, RG_BLOCK, 8192), R, dord.as<ull>() + k0, dmoff.as<ull>() + k0, nb,
+                    scratch.as<uint32_t>(), roff.as<ull>(), bound.as<ull>(), rop.as<uint8_t>(), rlen.as<uint32_t>(),
+                    nrun.as<ull>(), fdist.as<ull>(), bad.as<ull>(), t, needw.as<ull>(), bdone.as<ull>() + k0);
+          c.sync();
+          msband += c.t_al.ms();
+        }
+        hdone.resize(nr);
+        PG_HIP(hipMemcpyAsync(hdone.data(), bdone.p, 8 * nr, hipMemcpyDeviceToHost, c.stream));
+        c.sync();
+        std::vector<ull> left;                             // the pairs of this round that go on to 2 t
+        for (uint64_t i = 0; i < nr; ++i) {
+          ++nattempts;
+          bandcells += bcells(round[i], t);
+          if (hdone[i]) {
+            ++nbanded;
+            ++aligned;
+          } else if (bcells(round[i], 2ull * t) <= band_cap) {
+            left.push_back(round[i].j);
+          }
+        }
+        std::sort(left.begin(), left.end());
+        std::vector<Cand> next;
+        for (const Cand& x : alive)
+          if (x.k > k || std::binary_search(left.begin(), left.end(), x.j)) next.push_back(x);
+        alive.swap(next);
+      }
     }
     if (read_flags(c, bad))
       throw Error(-5, w + "the walk back over the direction bits does not agree with the fill");
@@ -771,6 +984,11 @@ void region_align(Ctx& c, uint64_t* n_pairs, uint64_t* n_aligned, uint64_t* n_op
   c.al_nl = nl;
   c.al_cells = cells;
   c.ms_al_fill = ms;
+  c.al_nover = nover;
+  c.al_nbanded = nbanded;
+  c.al_nattempts = nattempts;
+  c.al_bandcells = bandcells;
+  c.ms_al_band = msband;
   c.al_ready = true;
   if (n_pairs) *n_pairs = n;
   if (n_aligned) *n_aligned = aligned;

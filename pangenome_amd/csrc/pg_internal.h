@@ -388,6 +388,12 @@ struct Ctx {
   uint64_t al_cells_cap = 0;      // pg_tune: cells above which a pair is not aligned (0 = 2^24)
   uint64_t al_scratch = 0;        // pg_tune: bytes of direction bits per batch (0 = 256 MiB)
   int al_hash_bits = 0;           // pg_tune: low bits kept of a primitive's letters' hash (0 = all of it)
+  int al_band = 0;                // pg_tune: 1 = pairs above the cells cap are aligned in a band
+  uint64_t al_band_cap = 0;       // pg_tune: band cells above which a pair is given up (0 = 2^26)
+  uint64_t al_band_t0 = 0;        // pg_tune: the band's first threshold (0 = 64)
+  // the band form's part of the last pg_region_align (pg_region_align_band)
+  uint64_t al_nover = 0, al_nbanded = 0, al_nattempts = 0, al_bandcells = 0;
+  double ms_al_band = 0;
 
   // ---- npz persistence (pg_persist.hip)
   DevBuf preload;                 // staged PreEnt pairs, OR-merged by every build

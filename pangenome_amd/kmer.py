@@ -25,7 +25,7 @@ import numpy as np
 from collections.abc import Mapping
 
 from . import host
-from ._lib import Context, format_xyz
+from ._lib import PG_TUNE_ALIGN_BAND, Context, format_xyz
 
 
 class LabelTable(Mapping):
@@ -257,7 +257,8 @@ def rdbg_edges(g: DeviceGraph, Ns, chunk, rc, brkpt="", keep_on_device=False):
 
 def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_dict=None, saved=None,
               hashfunc=None, jit=True, chunk=2 ** 33, rc=False, cluster=True, out=None, min_weight=1, groups=None,
-              orders=0, links=False, seqs=False, inflation2=3, sites=False, bubbles=0, variants="", align=False):
+              orders=0, links=False, seqs=False, inflation2=3, sites=False, bubbles=0, variants="", align=False,
+              align_band=False):
     """:1853-1951: edge weights -> `<qry>_rdbg_weight.xyz` -> mcl (or reuse)
     -> label dictionary -> print the region rows.  The edges, the label
     table, the rows and both texts are made on the device; the host writes
@@ -295,7 +296,10 @@ def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_
     and `<qry>_fr_alleles.fa`, `_fr_alleles.tsv` and `_fr_variants.vcf` written.
     align (-A, with variants): every allele is then aligned against its
     site's reference on the device (pg_region_align) and `<qry>_fr_align.tsv`
-    and `_fr_primitives.vcf` written."""
+    and `_fr_primitives.vcf` written.  align_band (-L, with align): the pairs
+    above pg_region_align's cells cap are aligned in a band of diagonals
+    (PG_TUNE_ALIGN_BAND) instead of standing as one replacement; the same two
+    files."""
     out = out or sys.stdout
     g = rdbg_dict
     res = rdbg_edges(g, Ns, chunk, rc, brkpt=brkpt, keep_on_device=True)
@@ -377,7 +381,7 @@ def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_
             if variants:
                 write_variants(g, qry, names, flags, groups, variants)
                 if align:
-                    write_align(g, qry, names, flags, groups, variants)
+                    write_align(g, qry, names, flags, groups, variants, bool(align_band))
     gen = g.ctx.label_gen
     return LabelTable(loader=lambda: g.ctx.labels(gen))           # (raises once a later label pass replaced it)
 
@@ -540,14 +544,21 @@ def write_variants(g, qry, names, flags, groups, ref_name):
     host.write_variants_files(qry, fasta, table, ids, host.vcf_header(gnames[ref], contigs, gnames), vcf)
 
 
-def write_align(g, qry, names, flags, groups, ref_name):
+def write_align(g, qry, names, flags, groups, ref_name, band=False):
     """-A: the alleles just decoded (write_variants) aligned against their
     site's reference (pg_region_align) as `<qry>_fr_align.tsv` and the body
     of `_fr_primitives.vcf` (the device texts; a record is named by its
-    seqid), behind write_variants' header with an AC line."""
+    seqid), behind write_variants' header with an AC line.  band (-L): with
+    the pairs above the cells cap aligned in a band."""
     rec_group, gnames = host.assign_groups(names, flags, groups)
     ref = ref_genome(gnames, ref_name)
-    g.ctx.region_align()
+    if band:
+        g.ctx.tune(PG_TUNE_ALIGN_BAND, 1)
+    try:
+        g.ctx.region_align()
+    finally:
+        if band:
+            g.ctx.tune(PG_TUNE_ALIGN_BAND, 0)
     ids = [host.seqid(x) for x in names]
     contigs = [(ids[r], int(g.seq_len[r])) for r in np.flatnonzero(rec_group == ref).tolist()]
 
@@ -577,7 +588,10 @@ def manual_print(out=None):
                  "  -i: query sequences in fasta format", "  -k: kmer length",
                  "  -A: with -V, every allele aligned against the reference: CIGARs, and the SNVs and indels one per VCF line. 0 (off)",
                  "      or 1; single process only. writes <in>_fr_align.tsv, _fr_primitives.vcf",
-                 "  -d: the de bruijn graph", "  -r: break point of de bruijn graph",
+                 "  -d: the de bruijn graph",
+                 "  -L: with -A 1, the alleles too long for a whole alignment matrix (more than 2^24 cells) aligned in a band of",
+                 "      diagonals that doubles until it holds their distance, instead of one replacement. 0 (off) or 1",
+                 "  -r: break point of de bruijn graph",
                  "  -D: the reduced de bruijn graph", "  -R: break point of reduced de bruijn graph",
                  "  -v: with -g, the variable sites: pairs of regions joined in two or more ways, directly or through one region.",
                  "      0 (off) or 1; single process only. writes <in>_fr_sites.tsv, _fr_sites_genomes.tsv, _fr_sites.npz",
@@ -607,7 +621,7 @@ def parse_args(argv):
     """:1983-1997 — same flag handling, including `-k27` and skipped unknowns."""
     args = {"-i": "", "-k": "50", "-n": "2**63", "-r": "", "-d": "", "-R": "", "-D": "", "-c": "2", "-a": "mcl",
             "-w": "1", "-g": "", "-p": "0", "-l": "0", "-s": "0", "-I": "1.5", "-v": "0", "-b": "0",
-            "-V": "", "-A": "0"}
+            "-V": "", "-A": "0", "-L": "0"}
     N = len(argv)
     for i in range(1, N):
         k = argv[i]
@@ -707,6 +721,14 @@ def align_arg(args, variants):
     return None if args["-A"] == "1" and not variants else args["-A"] == "1"
 
 
+def band_arg(args, align):
+    """-L's value: False (0) or True (1), or None for a value that is refused
+    - anything else, or 1 without an accepted -A 1."""
+    if args["-L"] not in ("0", "1"):
+        return None
+    return None if args["-L"] == "1" and not align else args["-L"] == "1"
+
+
 def entry_point(argv, out=None, device=0):
     out = out or sys.stdout
     args = parse_args(argv)
@@ -716,8 +738,9 @@ def entry_point(argv, out=None, device=0):
     bubbles = bubbles_arg(args)
     variants = variants_arg(args, bubbles)
     align = align_arg(args, variants)
+    band = band_arg(args, align)
     bad = (not qry or n_orders is None or links is None or seqs is None or sites is None or bubbles is None or
-           variants is None or align is None)
+           variants is None or align is None or band is None)
     clu = None if bad else cluster_args(args)
     if clu is None:
         manual_print(out)
@@ -739,6 +762,8 @@ def entry_point(argv, out=None, device=0):
         clu["variants"] = variants
     if align:
         clu["align"] = True
+    if band:
+        clu["align_band"] = True
     # a group file, and -V's genome, are checked against the records before anything is built
     chk = (lambda g: check_groups(g, Ns, grp, variants)) if grp and (grp != "record" or variants) else None
     chunk = 2 ** 33
