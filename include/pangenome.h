@@ -530,6 +530,74 @@ int pg_freq_compare(pg_ctx* ctx, const uint64_t* bits, uint64_t n_labels, uint32
 int pg_freq_shared(pg_ctx* ctx, uint64_t* shared, uint64_t cap);              /* cap >= G * G      */
 int pg_freq_curve(pg_ctx* ctx, uint64_t* pan, uint64_t* core, uint64_t cap);  /* cap >= P * G each */
 
+/* ---- genome tree: the third thing a pangenome study draws from the
+ *      comparison - a tree of the genomes, by neighbour joining over a
+ *      distance matrix.  Integer only (fixed point); the result depends on
+ *      the input alone, whatever the schedule.
+ * Input: a distance matrix dist, uint64 [n][n], n <= 16384, in one of two forms.
+ * From the host: symmetric, with a zero diagonal and no entry above 2^31.
+ * dist == NULL: formed on the device from the `shared` matrix of the last
+ * successful pg_freq_compare where it lies; n must equal its G, and
+ *   d(g, h) = shared[g][g] + shared[h][h] - 2 shared[g][h],
+ * the labels in exactly one of the two genomes: a Hamming distance, so a
+ * metric, and at most 2^31 because pg_freq caps L at 2^31.
+ * Fixed point: S = 16 fractional bits, D = d << S.  Every value is a signed
+ * 64-bit integer; `>>` is an arithmetic shift and `/` is floor division, both
+ * rounding towards minus infinity (as Python's >> and // do).
+ * Slots: slot i holds leaf i at first.  Leaves have the node ids 0 .. n - 1,
+ * internal nodes are numbered n, n + 1, .. in join order.  A live slot keeps
+ * its position for the whole run.
+ * One join, while more than 3 slots are live (m = the number of live slots):
+ *   r_i = the sum over the live k of D[i][k];
+ *   Q(i, j) = (m - 2) D[i][j] - r_i - r_j for the live i < j;
+ *   the pair with the smallest Q is joined - among equal Q the smallest i,
+ *   then the smallest j;
+ *   len_i = clamp((D[i][j] + (r_i - r_j) / (m - 2)) >> 1, 0, D[i][j]),
+ *   len_j = D[i][j] - len_i; the join record is (node[i], node[j], len_i, len_j);
+ *   for every other live k, D[i][k] = D[k][i] = max(0, (D[i][k] + D[j][k] - D[i][j]) >> 1);
+ *   slot i now holds the new internal node and slot j is dead.
+ * The end: three live slots a < b < c are the three children of the root,
+ * each length on its own: x_a = max(0, (D_ab + D_ac - D_bc) >> 1), x_b and x_c
+ * likewise.  n = 2: two children, x_a = D_ab >> 1 and x_b = D_ab - x_a.  n = 1:
+ * one child of length 0.  n = 0: an empty result (no join, no child).
+ * There are max(n - 3, 0) joins.
+ * Why 64 bits hold it: D < 2^47 at the start (d <= 2^31, S = 16), and the
+ * clamped update never exceeds max(D[i][k], D[j][k]) (D[i][j] >= 0), so the
+ * bound holds throughout.  With m <= 2^14, r and (m - 2) D stay below 2^61, so
+ * |Q| < 2^63.
+ * Exactness: on an additive matrix - the path lengths of a tree with integer
+ * edge lengths - every division above is exact (every D is a multiple of
+ * 2^S, and the sums that are halved or divided are the even / divisible ones
+ * of the textbook method), so the tree and its lengths come back exactly:
+ * every length is a multiple of 2^S and they sum to the tree's length.
+ * (Checked on the host specification on 200 random trees of 4 to 40 leaves.)
+ * Device memory: 8 n^2 + O(n) bytes while the call runs (one matrix holds the
+ * working D in its upper triangle and the d that came in below it); the
+ * 8 n^2 of d stay until the next successful pg_tree_nj.  Three plain launches
+ * per join on the context's stream.
+ * Lifetime: the tree is a copy and stays until the next successful
+ * pg_tree_nj; pg_freq, pg_freq_compare and every region pass neither read nor
+ * drop it, nor it theirs.
+ * PG_EINVAL, the previous tree kept: a NULL context; dist == NULL before any
+ * pg_freq_compare or with another n than its G; a host matrix that is not
+ * symmetric, has a non-zero diagonal or an entry above 2^31 (found by a device
+ * reduction before anything is replaced).  n > 16384 is PG_ERANGE, decided
+ * before the matrix is read.  An allocation failure is PG_ENOMEM with the
+ * previous tree kept.  n_joins may be NULL. */
+int pg_tree_nj(pg_ctx* ctx, const uint64_t* dist, uint32_t n, uint64_t* n_joins);
+/* The results of the last pg_tree_nj: PG_EINVAL before any, PG_ERANGE for a
+ * short cap (entries).  Every output may be NULL.  pg_tree_dist: the d the
+ * tree was built from, [n][n], cap >= n * n.  pg_tree_joins: per join the two
+ * nodes joined (the left is slot i's, the right slot j's) and their lengths
+ * with S fractional bits, cap >= max(n - 3, 0).  pg_tree_root: the number of
+ * the root's children (min(n, 3)), their nodes and lengths, the unused
+ * entries 0.  pg_tree_time: HIP events over the joins, and cells = the sum of
+ * m^2 over them. */
+int pg_tree_dist(pg_ctx* ctx, uint64_t* dist, uint64_t cap);
+int pg_tree_joins(pg_ctx* ctx, uint32_t* left, uint32_t* right, uint64_t* left_len, uint64_t* right_len, uint64_t cap);
+int pg_tree_root(pg_ctx* ctx, uint32_t* n_children, uint32_t child[3], uint64_t len[3]);
+int pg_tree_time(pg_ctx* ctx, double* ms, uint64_t* cells);
+
 /* ---- region graph: which region follows which along a genome - the other
  *      half of a pangenome result next to the frequency table.  Nodes are the
  *      labels, links the ordered pairs of labels on adjacent rows of one walk,
@@ -1220,6 +1288,11 @@ uint64_t pg_format_rows(const int64_t* rows5, uint64_t n, const char* names, con
  * (default) = 64.  For tests: at 1 the band's edges and the doubling show on
  * cores of a few dozen letters. */
 #define PG_TUNE_ALIGN_BAND_T0 31
+/* PG_TUNE_NJ_BLOCKS: blocks of pg_tree_nj's arg-min pass.  0 (default) = by
+ * size: a wave per row, up to four blocks per compute unit; 1 .. 4096 = that
+ * many, so that a small input runs the reduction across blocks.  The result
+ * is the same at any value. */
+#define PG_TUNE_NJ_BLOCKS 32
 int pg_tune(pg_ctx* ctx, int what, int64_t value);
 
 /* Device bytes the library's buffers hold in this process now (peak == 0)

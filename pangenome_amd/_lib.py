@@ -46,6 +46,7 @@ PG_TUNE_ALIGN_HASH_BITS = 28    # 0 the full hash of a primitive's letters; 1..6
 PG_TUNE_ALIGN_BAND = 29         # pg_region_align: 1 = the pairs above the cells cap are aligned in a band of diagonals
 PG_TUNE_ALIGN_BAND_CELLS = 30   # the band form: a pair is given up before a band of more cells than this (0 = 2^26)
 PG_TUNE_ALIGN_BAND_T0 = 31      # the band form: the first threshold, doubled until it holds the distance (0 = 64)
+PG_TUNE_NJ_BLOCKS = 32          # pg_tree_nj: blocks of the arg-min pass (0 = by size); the result is the same at any value
 
 
 class PgStats(C.Structure):
@@ -122,6 +123,11 @@ SIGNATURES = {
     "pg_freq_compare": (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, _P, C.c_uint32]),
     "pg_freq_shared": (C.c_int, [_P, _P, C.c_uint64]),
     "pg_freq_curve": (C.c_int, [_P, _P, _P, C.c_uint64]),
+    "pg_tree_nj": (C.c_int, [_P, _P, C.c_uint32, _U64P]),
+    "pg_tree_dist": (C.c_int, [_P, _P, C.c_uint64]),
+    "pg_tree_joins": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64]),
+    "pg_tree_root": (C.c_int, [_P, C.POINTER(C.c_uint32), _P, _P]),
+    "pg_tree_time": (C.c_int, [_P, C.POINTER(C.c_double), _U64P]),
     "pg_region_graph": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, C.c_uint32, _U64P, _U64P, _U64P, _U64P]),
     "pg_region_nodes": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64]),
     "pg_region_links": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64]),
@@ -841,6 +847,57 @@ class Context:
         pan, core = np.empty((P, G), np.uint64), np.empty((P, G), np.uint64)
         check(self.lib.pg_freq_curve(self.h, ptr(pan), ptr(core), P * G), "pg_freq_curve")
         return pan, core
+
+    # ---------------------------------------------------- genome tree
+    def tree_nj(self, dist=None, n=None) -> int:
+        """The neighbour-joining tree (pg_tree_nj) of a host distance matrix
+        uint64 [n, n] (symmetric, zero diagonal, entries <= 2^31), or, dist
+        None, of the distances the device forms from the last freq_compare()'s
+        shared matrix (n defaults to its genomes).  Returns the number of
+        joins; the tree stays in the context (tree_dist / tree_joins /
+        tree_root)."""
+        if dist is None:
+            d, n = None, int(getattr(self, "cmp_groups_n", 0) if n is None else n)
+        else:
+            d = np.ascontiguousarray(dist, dtype=np.uint64)
+            n = int(d.shape[0] if n is None else n)
+            if d.size < n * n or not d.size:
+                d = np.concatenate([d.reshape(-1), np.zeros(1, np.uint64)])   # (never NULL; too large an n is refused unread)
+        nj = C.c_uint64()
+        check(self.lib.pg_tree_nj(self.h, ptr(d), n, C.byref(nj)), "pg_tree_nj")
+        self.tree_n = n
+        return nj.value
+
+    def tree_dist(self) -> np.ndarray:
+        """The distances the tree was built from, uint64 [n, n] (pg_tree_dist)."""
+        n = getattr(self, "tree_n", 0)
+        d = np.empty((n, n), np.uint64)
+        check(self.lib.pg_tree_dist(self.h, ptr(d), n * n), "pg_tree_dist")
+        return d
+
+    def tree_joins(self) -> dict:
+        """The joins in order: left, right (uint32 node ids; leaves 0 .. n - 1,
+        join t makes node n + t), left_len, right_len (uint64, 16 fractional
+        bits) (pg_tree_joins)."""
+        J = max(getattr(self, "tree_n", 0) - 3, 0)
+        t = {"left": np.empty(J, np.uint32), "right": np.empty(J, np.uint32),
+             "left_len": np.empty(J, np.uint64), "right_len": np.empty(J, np.uint64)}
+        check(self.lib.pg_tree_joins(self.h, *[ptr(a) for a in t.values()], J), "pg_tree_joins")
+        return t
+
+    def tree_root(self):
+        """(child, len): the root's children (uint32, at most 3) and their
+        lengths (uint64, 16 fractional bits) (pg_tree_root)."""
+        nc, child, ln = C.c_uint32(), np.zeros(3, np.uint32), np.zeros(3, np.uint64)
+        check(self.lib.pg_tree_root(self.h, C.byref(nc), ptr(child), ptr(ln)), "pg_tree_root")
+        return child[:nc.value].copy(), ln[:nc.value].copy()
+
+    def tree_time(self):
+        """(ms, cells): the joins' time in the last tree_nj() and the sum of
+        m^2 over them (pg_tree_time)."""
+        ms, n = C.c_double(), C.c_uint64()
+        check(self.lib.pg_tree_time(self.h, C.byref(ms), C.byref(n)), "pg_tree_time")
+        return ms.value, n.value
 
     # ---------------------------------------------------- region graph
     def region_graph(self, rec_group, n_groups: int, rows=None):

@@ -96,7 +96,7 @@ void pg_destroy(pg_ctx* x) {
                         &c.k3_hint, &c.part_cnt, &c.tile_cnt, &c.tile_off, &c.occ, &c.edge_tab, &c.pair_tab,
                         &c.edge_out, &c.edge_exp, &c.lab_tab, &c.lab_list, &c.rows_buf, &c.xyz_off,
                         &c.text_buf, &c.clu_text, &c.mk_mat, &c.fr_tab, &c.fr_spec, &c.fr_grp, &c.fr_text,
-                        &c.cmp_shared, &c.cmp_curve, &c.rg_nodes, &c.rg_links, &c.rg_paths, &c.rg_steps, &c.rg_text,
+                        &c.cmp_shared, &c.cmp_curve, &c.nj_dist, &c.rg_nodes, &c.rg_links, &c.rg_paths, &c.rg_steps, &c.rg_text,
                         &c.rs_tab, &c.rs_blob, &c.preload,
                         &c.dump_cnt};
   for (auto* b : bufs) b->release();
@@ -111,6 +111,7 @@ void pg_destroy(pg_ctx* x) {
   c.t1.destroy();
   c.t6.destroy();
   c.t_rs.destroy();
+  c.t_nj.destroy();
   for (auto& e : c.ev)
     if (e) (void)hipEventDestroy(e);
   for (auto e : c.cev)
@@ -435,6 +436,10 @@ int pg_tune(pg_ctx* x, int what, int64_t value) {
       case PG_TUNE_STAGE_SLOTS:
         if (value < 0 || value == 1 || value > 8) throw pg::Error(PG_EINVAL, "pg_tune: staging slots must be 0 or 2..8");
         x->c.stage_slots = value ? (uint64_t)value : 4;
+        break;
+      case PG_TUNE_NJ_BLOCKS:
+        if (value < 0 || value > 4096) throw pg::Error(PG_EINVAL, "pg_tune: arg-min blocks must be in [0, 4096]");
+        x->c.nj_blocks = (int)value;
         break;
       default:
         throw pg::Error(PG_EINVAL, "pg_tune: unknown parameter " + std::to_string(what));
@@ -898,6 +903,43 @@ int pg_freq_curve(pg_ctx* x, uint64_t* pan, uint64_t* core, uint64_t cap) {
     if (!x) throw pg::Error(PG_EINVAL, "pg_freq_curve: ctx is NULL");
     PG_HIP(hipSetDevice(x->c.device));
     pg::freq_curve(x->c, pan, core, cap);
+  });
+}
+
+int pg_tree_nj(pg_ctx* x, const uint64_t* dist, uint32_t n, uint64_t* n_joins) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_tree_nj: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::tree_nj(x->c, dist, n, n_joins);
+  });
+}
+
+int pg_tree_dist(pg_ctx* x, uint64_t* dist, uint64_t cap) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_tree_dist: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::tree_dist(x->c, dist, cap);
+  });
+}
+
+int pg_tree_joins(pg_ctx* x, uint32_t* left, uint32_t* right, uint64_t* left_len, uint64_t* right_len, uint64_t cap) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_tree_joins: ctx is NULL");
+    pg::tree_joins(x->c, left, right, left_len, right_len, cap);
+  });
+}
+
+int pg_tree_root(pg_ctx* x, uint32_t* n_children, uint32_t child[3], uint64_t len[3]) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_tree_root: ctx is NULL");
+    pg::tree_root(x->c, n_children, child, len);
+  });
+}
+
+int pg_tree_time(pg_ctx* x, double* ms, uint64_t* cells) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_tree_time: ctx is NULL");
+    pg::tree_time(x->c, ms, cells);
   });
 }
 

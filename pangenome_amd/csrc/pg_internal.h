@@ -323,6 +323,18 @@ struct Ctx {
   bool cmp_ready = false;         // (a successful pg_freq clears it: the result described the old table)
   uint64_t cmp_chunk = 0;         // pg_tune: label-axis words per k_cmp_shared block (0 = by size)
   int cmp_form = 0;               // pg_tune: curves (0 = LDS counters up to CMP_LDS_GROUPS genomes, 1 = global atomics)
+  // ---- genome tree (pg_tree.hip): the result of the last pg_tree_nj (no other pass reads or drops it)
+  DevBuf nj_dist;                 // uint64 [n][n]: the distances the tree was built from
+  std::vector<uint32_t> nj_join;  // [2][J]: left, right node of every join (the tables are a few bytes per leaf: host)
+  std::vector<uint64_t> nj_len;   // [2][J]: their lengths, 16 fractional bits
+  std::vector<uint32_t> nj_root;  // n_children, child [3]
+  std::vector<uint64_t> nj_rlen;  // [3]
+  uint32_t nj_n = 0;
+  bool nj_ready = false;
+  Timer t_nj;                     // the joins of the last pg_tree_nj
+  double ms_nj = 0;
+  uint64_t nj_cells = 0;          // the sum of m^2 over its joins
+  int nj_blocks = 0;              // pg_tune: blocks of the arg-min pass (0 = by size)
   // ---- region graph (pg_region.hip): the result of the last pg_region_graph
   DevBuf rg_nodes;                // [n] label, rows, max length; uint32 [n] links out, links in
   DevBuf rg_links;                // [n] from, to, count; uint32 [n] genomes
@@ -553,6 +565,16 @@ void freq_compare(Ctx& c, const uint64_t* h_bits, uint64_t n_labels, uint32_t n_
                   uint32_t n_orders);
 void freq_shared(Ctx& c, uint64_t* shared, uint64_t cap);
 void freq_curve(Ctx& c, uint64_t* pan, uint64_t* core, uint64_t cap);
+
+// pg_tree.hip
+// The neighbour-joining tree of a distance matrix (h_dist NULL: formed from the
+// last freq_compare's shared matrix on the device); replaces the context's
+// previous tree only when it succeeds.
+void tree_nj(Ctx& c, const uint64_t* h_dist, uint32_t n, uint64_t* n_joins);
+void tree_dist(Ctx& c, uint64_t* dist, uint64_t cap);
+void tree_joins(Ctx& c, uint32_t* left, uint32_t* right, uint64_t* left_len, uint64_t* right_len, uint64_t cap);
+void tree_root(Ctx& c, uint32_t* n_children, uint32_t* child, uint64_t* len);
+void tree_time(Ctx& c, double* ms, uint64_t* cells);
 
 // pg_region.hip: the front end the passes over the region rows share (pg_freq, pg_region_graph,
 // pg_region_seqs; device side in pg_region.h)

@@ -1539,9 +1539,11 @@ def entry_point(argv, out=None, shard_factory=None, device=None, dev_index: int 
     # so is -s (the region sequences): a label's representative may lie in another rank's records; and -v (the
     # variable sites), whose alleles need the ranks' per-(allele, genome) records, and -b (the sites between anchors),
     # whose anchors need every rank's genomes of a label, and -V (their alleles as sequences), which reads them, and
-    # -A (the alleles' alignments), which reads -V's, and -L (their band form), which needs -A
+    # -A (the alleles' alignments), which reads -V's, and -L (their band form), which needs -A, and -T (the genome
+    # tree), which reads one process's comparison
     bad = (not qry or n_orders is None or args["-l"] != "0" or args["-s"] != "0" or args["-v"] != "0" or
-           args["-b"] != "0" or args["-V"] != "" or args["-A"] != "0" or args["-L"] != "0")
+           args["-b"] != "0" or args["-V"] != "" or args["-A"] != "0" or args["-L"] != "0" or
+           args["-T"] != "0")
     clu = None if bad else cluster_args(args)
     if clu is None:
         if dist.get_rank() == 0:

@@ -1079,6 +1079,164 @@ def write_compare_files(prefix: str, names, shared, orders, pan, core) -> None:
     whole("_fr_compare.npz", lambda f: np.savez(f, genomes=gn, shared=s, orders=o, pan=pan, core=core))
 
 
+# ---------------------------------------------------------------- genome tree
+TREE_FRAC_BITS = 16
+TREE_MAX_LEAVES = 16384
+TREE_MAX_DIST = 1 << 31
+
+
+def tree_nj(dist):
+    """The genome tree's specification (pg_tree_nj computes the same on the
+    device; include/pangenome.h, "genome tree", has the definition).  dist:
+    [n, n] non-negative integers, symmetric, zero diagonal, no entry above
+    2^31, n <= 16384 (ValueError otherwise).  Returns (joins, root): joins a
+    dict of left, right (uint32 [J], J = max(n - 3, 0)) and left_len, right_len
+    (uint64 [J], 16 fractional bits); root = (child uint32 [<= 3], len uint64).
+    Integers only: the matrix and the row sums are int64 arrays, which the
+    header's bound (|Q| < 2^63) keeps exact, `>>` and `//` round towards minus
+    infinity, and the scalars of a join are Python integers.  The live slots
+    are kept dense in their order (a dead slot's row and column are deleted),
+    so the first minimum of the row-major upper triangle is the smallest
+    (i, j) among equal Q."""
+    d = np.ascontiguousarray(dist, dtype=_U64)
+    n = d.shape[0]
+    if n > TREE_MAX_LEAVES:
+        raise ValueError("tree_nj: %d leaves, at most %d" % (n, TREE_MAX_LEAVES))
+    d = d.reshape(n, n)
+    if n and int(d.max()) > TREE_MAX_DIST:
+        raise ValueError("tree_nj: an entry above 2^31")
+    if d.diagonal().any():
+        raise ValueError("tree_nj: a non-zero diagonal")
+    if not np.array_equal(d, d.T):
+        raise ValueError("tree_nj: the matrix is not symmetric")
+    S = TREE_FRAC_BITS
+    D = d.astype(np.int64) << S
+    r = D.sum(axis=1)
+    node = np.arange(n, dtype=np.int64)
+    J = max(n - 3, 0)
+    joins = {"left": np.zeros(J, np.uint32), "right": np.zeros(J, np.uint32),
+             "left_len": np.zeros(J, _U64), "right_len": np.zeros(J, _U64)}
+    low = np.tri(n, dtype=bool) if J else None           # (on and below the diagonal: no pair)
+    big = np.iinfo(np.int64).max
+    for t in range(J):
+        m = n - t
+        Q = (m - 2) * D - r[:, None] - r[None, :]
+        Q[low[:m, :m]] = big
+        i, j = divmod(int(np.argmin(Q)), m)
+        dij = int(D[i, j])
+        li = min(max((dij + (int(r[i]) - int(r[j])) // (m - 2)) >> 1, 0), dij)
+        joins["left"][t], joins["right"][t] = node[i], node[j]
+        joins["left_len"][t], joins["right_len"][t] = li, dij - li
+        new = np.maximum(0, (D[i] + D[j] - dij) >> 1)
+        new[i] = new[j] = 0
+        r += new - D[i] - D[j]
+        r[i] = int(new.sum())
+        D[i, :] = new
+        D[:, i] = new
+        node[i] = n + t
+        D = np.delete(np.delete(D, j, axis=0), j, axis=1)
+        r, node = np.delete(r, j), np.delete(node, j)
+    D = [[int(v) for v in row] for row in D.tolist()]
+    if n >= 3:
+        (a, b, c) = (0, 1, 2)
+        ln = [max(0, (D[a][b] + D[a][c] - D[b][c]) >> 1), max(0, (D[a][b] + D[b][c] - D[a][c]) >> 1),
+              max(0, (D[a][c] + D[b][c] - D[a][b]) >> 1)]
+    elif n == 2:
+        ln = [D[0][1] >> 1, D[0][1] - (D[0][1] >> 1)]
+    else:
+        ln = [0] * n
+    return joins, (node.astype(np.uint32), np.array(ln, dtype=_U64))
+
+
+def tree_len_text(v: int) -> bytes:
+    """A length of 16 fractional bits as the tree files print it: six
+    decimals, cut and not rounded."""
+    v = int(v)
+    return b"%d.%06d" % (v >> TREE_FRAC_BITS, ((v & 65535) * 1000000) >> TREE_FRAC_BITS)
+
+
+def tree_name_text(name) -> bytes:
+    """A leaf's name as the Newick text holds it: verbatim, or in single
+    quotes with the inner quotes doubled if it has one of ()[]{}:;,'" or
+    white space."""
+    nm = name.encode() if isinstance(name, str) else bytes(name)
+    if any(ch in b"()[]{}:;,'\" \t\n\r\x0b\x0c" for ch in nm):
+        return b"'" + nm.replace(b"'", b"''") + b"'"
+    return nm
+
+
+def tree_newick(names, joins, root) -> bytes:
+    """The Newick text of tree_nj's (or the device's) tables over the leaves
+    called names: `(<child>:<len>,<child>:<len>,<child>:<len>);` and a line
+    feed, nested, each join's left child before its right.  No leaf: empty."""
+    n = len(names)
+    if not n:
+        return b""
+    left, right = [int(x) for x in joins["left"]], [int(x) for x in joins["right"]]
+    ll, rl = [int(x) for x in joins["left_len"]], [int(x) for x in joins["right_len"]]
+    out = []
+    # (an explicit stack: a comb of 16384 leaves is as deep as it is long)
+    stack = [b");\n"]
+    kids = list(zip([int(x) for x in root[0]], [int(x) for x in root[1]]))
+    for k, (c, v) in reversed(list(enumerate(kids))):
+        stack.append(b":" + tree_len_text(v) + (b"," if k + 1 < len(kids) else b""))
+        stack.append(c)
+    out.append(b"(")
+    while stack:
+        x = stack.pop()
+        if isinstance(x, bytes):
+            out.append(x)
+        elif x < n:
+            out.append(tree_name_text(names[x]))
+        else:
+            t = x - n
+            stack.append(b":" + tree_len_text(rl[t]) + b")")
+            stack.append(right[t])
+            stack.append(b":" + tree_len_text(ll[t]) + b",")
+            stack.append(left[t])
+            out.append(b"(")
+    return b"".join(out)
+
+
+def write_tree_files(prefix: str, names, dist, joins, root, var: bool = False) -> None:
+    """The `-T` files of `prefix` (the input's path): `_fr_dist.tsv` (the
+    distance matrix in `_fr_shared.tsv`'s layout), `_fr_tree.nwk`,
+    `_fr_tree.tsv` (per join the node it makes, its two children and their
+    lengths as the Newick prints them, then one `#root` line: the children,
+    then their lengths) and `_fr_tree.npz`; var: the tree of the differences,
+    `_fr_vardist.tsv` and `_fr_vartree.nwk` alone.  Each is written to `.tmp`
+    and renamed when whole."""
+    d = np.asarray(dist, _U64)
+    n = d.shape[0]
+    nm = [bytes(x) for x in names]
+
+    def whole(suffix, fill):
+        fn = prefix + suffix
+        with open(fn + ".tmp", "wb") as f:
+            fill(f)
+        os.replace(fn + ".tmp", fn)
+    head = b"#genome" + b"".join(b"\t" + x for x in nm) + b"\n"
+    dl = d.tolist()
+    whole("_fr_vardist.tsv" if var else "_fr_dist.tsv", lambda f: f.write(head + b"".join(
+        nm[g] + "".join("\t%d" % v for v in dl[g]).encode() + b"\n" for g in range(n))))
+    whole("_fr_vartree.nwk" if var else "_fr_tree.nwk", lambda f: f.write(tree_newick(nm, joins, root)))
+    if var:
+        return
+    cols = [[int(x) for x in joins[k]] for k in ("left", "right", "left_len", "right_len")]
+    child, ln = [int(x) for x in root[0]], [int(x) for x in root[1]]
+    whole("_fr_tree.tsv", lambda f: f.write(
+        b"#node\tleft\tright\tleft_len\tright_len\n" + b"".join(
+            b"%d\t%d\t%d\t%s\t%s\n" % (n + t, a, b, tree_len_text(x), tree_len_text(y))
+            for t, (a, b, x, y) in enumerate(zip(*cols))) +
+        b"#root" + b"".join(b"\t%d" % c for c in child) + b"".join(b"\t" + tree_len_text(v) for v in ln) + b"\n"))
+    gn = np.array(nm, dtype=np.bytes_) if nm else np.zeros(0, "S1")
+    whole("_fr_tree.npz", lambda f: np.savez(
+        f, genomes=gn, dist=d, left=np.asarray(joins["left"], np.uint32), right=np.asarray(joins["right"], np.uint32),
+        left_len=np.asarray(joins["left_len"], _U64), right_len=np.asarray(joins["right_len"], _U64),
+        root_child=np.asarray(root[0], np.uint32), root_len=np.asarray(root[1], _U64),
+        frac_bits=np.int64(TREE_FRAC_BITS)))
+
+
 REGION_COLS = (("labels", np.int64), ("rows", np.uint64), ("max_len", np.uint64), ("n_out", np.uint32),
                ("n_in", np.uint32), ("link_from", np.int64), ("link_to", np.int64), ("link_count", np.uint64),
                ("link_genomes", np.uint32), ("path_record", np.int64), ("path_strand", np.int64),

@@ -9,7 +9,7 @@ runs in libpangenome_hip.so on an MI355X (pangenome_amd/csrc).  Mirrors:
   dbg2rdbg     :1313-1321                rdBG (K5 degree scan + compaction)
   seq2graph    :1853-1951                edges -> .xyz -> mcl -> labels -> rows
   dump / load_on_disk  :243-335         `<in>_db.npz` (oakht slot layout)
-  entry_point  :1971-2146                CLI (-i -k -n -c -r -d -R -D; ours: -a -w -g -p -l -s -v -b -V)
+  entry_point  :1971-2146                CLI (-i -k -n -c -r -d -R -D; ours: -a -w -g -p -l -s -v -b -V -A -L -T)
 
 Usage:  python -m pangenome_amd -i genomes.fa -k 27 > result.tab
 """
@@ -258,7 +258,7 @@ def rdbg_edges(g: DeviceGraph, Ns, chunk, rc, brkpt="", keep_on_device=False):
 def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_dict=None, saved=None,
               hashfunc=None, jit=True, chunk=2 ** 33, rc=False, cluster=True, out=None, min_weight=1, groups=None,
               orders=0, links=False, seqs=False, inflation2=3, sites=False, bubbles=0, variants="", align=False,
-              align_band=False):
+              align_band=False, tree=False):
     """:1853-1951: edge weights -> `<qry>_rdbg_weight.xyz` -> mcl (or reuse)
     -> label dictionary -> print the region rows.  The edges, the label
     table, the rows and both texts are made on the device; the host writes
@@ -299,7 +299,13 @@ def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_
     and `_fr_primitives.vcf` written.  align_band (-L, with align): the pairs
     above pg_region_align's cells cap are aligned in a band of diagonals
     (PG_TUNE_ALIGN_BAND) instead of standing as one replacement; the same two
-    files."""
+    files.  tree (-T, with groups): after the frequency and the comparison
+    files a neighbour-joining tree of the genomes is built on the device
+    (pg_tree_nj) from the comparison's shared matrix where it lies
+    (pg_freq_compare with no orders is run first if orders has not) and
+    `<qry>_fr_dist.tsv`, `_fr_tree.nwk`, `_fr_tree.tsv` and `_fr_tree.npz`
+    written; with align as well, a second tree from the primitive VCF lines'
+    carrier bits as `<qry>_fr_vartree.nwk` and `_fr_vardist.tsv`."""
     out = out or sys.stdout
     g = rdbg_dict
     res = rdbg_edges(g, Ns, chunk, rc, brkpt=brkpt, keep_on_device=True)
@@ -370,6 +376,8 @@ def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_
         gnames = write_freq(g, qry, names, flags, groups)
         if orders:
             write_compare(g, qry, gnames, int(orders))
+        if tree:
+            write_tree(g, qry, gnames, compared=bool(orders))
         if links:
             write_region(g, qry, names, flags, groups)
         if seqs:
@@ -382,6 +390,8 @@ def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_
                 write_variants(g, qry, names, flags, groups, variants)
                 if align:
                     write_align(g, qry, names, flags, groups, variants, bool(align_band))
+                    if tree:
+                        write_var_tree(g, qry, gnames)
     gen = g.ctx.label_gen
     return LabelTable(loader=lambda: g.ctx.labels(gen))           # (raises once a later label pass replaced it)
 
@@ -436,6 +446,30 @@ def write_compare(g, qry, gnames, n_orders):
     g.ctx.freq_compare(orders)
     pan, core = g.ctx.freq_curves()
     host.write_compare_files(qry, gnames, g.ctx.freq_shared(), orders, pan, core)
+
+
+def write_tree(g, qry, gnames, compared):
+    """-T: the neighbour-joining tree of the genomes (pg_tree_nj) from the
+    shared matrix of the comparison where it lies on the device - write_compare's
+    (compared), or one made here over no orders - as `<qry>_fr_dist.tsv`,
+    `_fr_tree.nwk`, `_fr_tree.tsv` and `_fr_tree.npz`."""
+    if not compared:
+        g.ctx.freq_compare(None)
+    g.ctx.tree_nj()
+    host.write_tree_files(qry, gnames, g.ctx.tree_dist(), g.ctx.tree_joins(), g.ctx.tree_root())
+
+
+def write_var_tree(g, qry, gnames):
+    """-T with -A: a second tree, from the differences: the carrier bits of
+    the primitive VCF lines just written (write_align) compared as presence
+    rows (pg_freq_compare, no orders; this replaces the device's comparison,
+    whose files are written by now), d(g, h) = the lines carried by exactly
+    one of the two genomes - a genome with no allele at a site carries none of
+    its lines - as `<qry>_fr_vartree.nwk` and `_fr_vardist.tsv`."""
+    G = len(gnames)
+    g.ctx.freq_compare(None, bits=g.ctx.region_align_lines(G)["bits"], n_groups=G)
+    g.ctx.tree_nj()
+    host.write_tree_files(qry, gnames, g.ctx.tree_dist(), g.ctx.tree_joins(), g.ctx.tree_root(), var=True)
 
 
 def write_region(g, qry, names, flags, groups):
@@ -592,6 +626,9 @@ def manual_print(out=None):
                  "  -L: with -A 1, the alleles too long for a whole alignment matrix (more than 2^24 cells) aligned in a band of",
                  "      diagonals that doubles until it holds their distance, instead of one replacement. 0 (off) or 1",
                  "  -r: break point of de bruijn graph",
+                 "  -T: with -g, a neighbour-joining tree of the genomes from the regions they share. 0 (off) or 1; single process only.",
+                 "      writes <in>_fr_dist.tsv, _fr_tree.nwk (Newick), _fr_tree.tsv, _fr_tree.npz and, with -A 1, a second tree from",
+                 "      the primitive VCF lines: <in>_fr_vartree.nwk, _fr_vardist.tsv",
                  "  -D: the reduced de bruijn graph", "  -R: break point of reduced de bruijn graph",
                  "  -v: with -g, the variable sites: pairs of regions joined in two or more ways, directly or through one region.",
                  "      0 (off) or 1; single process only. writes <in>_fr_sites.tsv, _fr_sites_genomes.tsv, _fr_sites.npz",
@@ -621,7 +658,7 @@ def parse_args(argv):
     """:1983-1997 — same flag handling, including `-k27` and skipped unknowns."""
     args = {"-i": "", "-k": "50", "-n": "2**63", "-r": "", "-d": "", "-R": "", "-D": "", "-c": "2", "-a": "mcl",
             "-w": "1", "-g": "", "-p": "0", "-l": "0", "-s": "0", "-I": "1.5", "-v": "0", "-b": "0",
-            "-V": "", "-A": "0", "-L": "0"}
+            "-V": "", "-A": "0", "-L": "0", "-T": "0"}
     N = len(argv)
     for i in range(1, N):
         k = argv[i]
@@ -729,6 +766,14 @@ def band_arg(args, align):
     return None if args["-L"] == "1" and not align else args["-L"] == "1"
 
 
+def tree_arg(args):
+    """-T's value: False (0) or True (1), or None for a value that is refused
+    - anything else, or 1 without -g."""
+    if args["-T"] not in ("0", "1"):
+        return None
+    return None if args["-T"] == "1" and not args["-g"] else args["-T"] == "1"
+
+
 def entry_point(argv, out=None, device=0):
     out = out or sys.stdout
     args = parse_args(argv)
@@ -739,7 +784,8 @@ def entry_point(argv, out=None, device=0):
     variants = variants_arg(args, bubbles)
     align = align_arg(args, variants)
     band = band_arg(args, align)
-    bad = (not qry or n_orders is None or links is None or seqs is None or sites is None or bubbles is None or
+    tree = tree_arg(args)
+    bad = (tree is None or not qry or n_orders is None or links is None or seqs is None or sites is None or bubbles is None or
            variants is None or align is None or band is None)
     clu = None if bad else cluster_args(args)
     if clu is None:
@@ -764,6 +810,8 @@ def entry_point(argv, out=None, device=0):
         clu["align"] = True
     if band:
         clu["align_band"] = True
+    if tree:
+        clu["tree"] = True
     # a group file, and -V's genome, are checked against the records before anything is built
     chk = (lambda g: check_groups(g, Ns, grp, variants)) if grp and (grp != "record" or variants) else None
     chunk = 2 ** 33
