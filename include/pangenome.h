@@ -598,6 +598,79 @@ int pg_tree_joins(pg_ctx* ctx, uint32_t* left, uint32_t* right, uint64_t* left_l
 int pg_tree_root(pg_ctx* ctx, uint32_t* n_children, uint32_t child[3], uint64_t len[3]);
 int pg_tree_time(pg_ctx* ctx, double* ms, uint64_t* cells);
 
+/* ---- tree support: how far every branch of the genome tree can be trusted,
+ *      by the bootstrap - the characters (the presence rows) are resampled
+ *      with replacement, the tree is rebuilt for every resample, and every
+ *      join of the real tree is rated by the number of replicate trees that
+ *      split the genomes the same way.  Integer only; the draws are
+ *      counter-based, so the result depends on (bits, seed, n_reps) and the
+ *      rated tree alone, whatever the schedule, the batch size or the form.
+ * Input: a presence table bits, uint64 [n_labels][W], exactly as
+ * pg_freq_compare takes it (bits == NULL: the last pg_freq's table where it
+ * lies; n_labels is then ignored and n_groups must equal that table's);
+ * n_reps = R in [1, 4096]; a 64-bit seed; and the context's last pg_tree_nj
+ * tree, whose joins are rated and whose n must equal n_groups.  L = n_labels.
+ * Draws: for replicate b in 0 .. R - 1 and draw t in 0 .. L - 1, x = output t
+ * of splitmix64 started at seed ^ ((b + 1) * 0xD1B54A32D192ED03) (synth.py's
+ * splitmix64(seed, b + 1, L): z = state + (t + 1) * 0x9E3779B97F4A7C15, then
+ * z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9, z = (z ^ z >> 27) *
+ * 0x94D049BB133111EB, x = z ^ z >> 31) - a pure function of (seed, b, t) -
+ * and idx(b, t) = ((x >> 32) * L) >> 32 in unsigned 64 bits (no wrap:
+ * L <= 2^31).  The replicate's characters are the rows bits[idx(b, 0)], ..,
+ * bits[idx(b, L - 1)].  L > 2^31 is PG_ERANGE.
+ * Replicate distance: d_b(g, h) = the draws t whose row has exactly one of
+ * the bits g, h set: a Hamming distance over the drawn rows, at most L <=
+ * 2^31, pg_tree_nj's input bound.  With L == 0 every d_b is 0 (the star's
+ * tie rule decides the tree).
+ * Replicate tree: the method of "genome tree" above applied to d_b, unchanged
+ * (16 fractional bits, floor shifts, the total order (Q, i, j), slots that
+ * keep their position).  Only the joins' (left, right) are kept.
+ * Splits: the clade of leaf i is {i}, that of node n + t the union of its two
+ * children's.  The split of join t is its clade if leaf 0 is not in it,
+ * otherwise the complement within 0 .. n - 1, held as W words.  A tree of
+ * n > 3 leaves has n - 3 joins and as many distinct, non-trivial splits.
+ * Support: support[t], uint32, t < J = max(n - 3, 0) = the replicates b whose
+ * tree has a join with the same split as join t of the rated tree (a hash
+ * pre-filters; a match counts only after all W words are equal).
+ * Guard: before any replicate runs, the un-resampled Hamming matrix of bits is
+ * formed by the same distance kernels (idx = the identity) and compared on the
+ * device with the rated tree's pg_tree_dist; a difference is PG_EINVAL ("the
+ * tree was not built from this table"), the previous support kept.
+ * PG_EINVAL, before any device work, the previous result kept: a NULL
+ * context; no tree; n_groups different from the tree's n; bits == NULL before
+ * any pg_freq or with another n_groups than its table's; R outside [1, 4096];
+ * a host row with a bit at or above n_groups.  An allocation failure is
+ * PG_ENOMEM with the previous result kept.
+ * rep_dist (for tests; NULL: not wanted): the full symmetric replicate
+ * matrices with zero diagonal, uint64 [R][n][n]; rep_dist_cap (cells) below
+ * R * n * n is PG_ERANGE, decided before any device work.  Nothing of size
+ * R x n^2 is kept after the call.
+ * Device work, in batches of replicates that fit PG_TUNE_BOOT_SCRATCH bytes:
+ * draw + gather + transpose in one pass, a batched Hamming "popcount GEMM",
+ * every replicate's whole neighbour joining by one workgroup (the matrix in
+ * LDS up to n = 128, in global scratch above it while enough replicates run
+ * side by side, pg_tree_nj's per-join launches otherwise; PG_TUNE_BOOT_FORM),
+ * then clades and matching.
+ * Lifetime: the support and the replicate joins are small host-side copies
+ * and stay until the next successful pg_tree_bootstrap; a successful
+ * pg_tree_nj drops them (they described the old tree: the exports below then
+ * return PG_EINVAL). */
+int pg_tree_bootstrap(pg_ctx* ctx, const uint64_t* bits, uint64_t n_labels, uint32_t n_groups, uint32_t n_reps,
+                      uint64_t seed, uint64_t* rep_dist /* NULL or [R][n][n] */, uint64_t rep_dist_cap);
+/* The results of the last pg_tree_bootstrap: PG_EINVAL before any (or after a
+ * later pg_tree_nj), PG_ERANGE for a short cap (entries).  Every output may be
+ * NULL.  pg_tree_support: support [J], cap >= J, and R.
+ * pg_tree_bootstrap_joins: every replicate's joins, uint32 [R][J] each, cap >=
+ * R * J.  pg_tree_bootstrap_time: HIP events over the batches' distance
+ * passes, joins, and clade / matching passes, and cells = R x the sum of m^2
+ * over a tree's joins.  pg_tree_bootstrap_form: which form of the neighbour
+ * joining ran (1, 2 or 3 as PG_TUNE_BOOT_FORM numbers them; 0: n <= 3, there
+ * was no join) and the number of batches. */
+int pg_tree_support(pg_ctx* ctx, uint32_t* support, uint64_t cap, uint32_t* n_reps);
+int pg_tree_bootstrap_joins(pg_ctx* ctx, uint32_t* left, uint32_t* right, uint64_t cap);
+int pg_tree_bootstrap_time(pg_ctx* ctx, double* ms_dist, double* ms_nj, double* ms_support, uint64_t* cells);
+int pg_tree_bootstrap_form(pg_ctx* ctx, uint32_t* form, uint32_t* n_batches);
+
 /* ---- region graph: which region follows which along a genome - the other
  *      half of a pangenome result next to the frequency table.  Nodes are the
  *      labels, links the ordered pairs of labels on adjacent rows of one walk,
@@ -1293,6 +1366,20 @@ uint64_t pg_format_rows(const int64_t* rows5, uint64_t n, const char* names, con
  * many, so that a small input runs the reduction across blocks.  The result
  * is the same at any value. */
 #define PG_TUNE_NJ_BLOCKS 32
+/* PG_TUNE_BOOT_SCRATCH: device bytes of one batch of pg_tree_bootstrap's
+ * replicates (their bit rows, matrices and clades).  0 (default) = 256 MiB;
+ * a batch always holds at least one replicate.  For tests: a small value
+ * forces batches of one, or a ragged last batch.  The result is the same at
+ * any value. */
+#define PG_TUNE_BOOT_SCRATCH 33
+/* PG_TUNE_BOOT_FORM: how pg_tree_bootstrap runs a replicate's neighbour
+ * joining.  0 (default) = by size, as measured: form 1 up to 128 leaves,
+ * form 2 up to 256 leaves with 4 or more replicates and up to 512 with 16 or
+ * more, form 3 otherwise; 1 = one workgroup with the matrix in LDS (n <= 128;
+ * above it as 0); 2 = one workgroup with the matrix in global scratch (n <=
+ * 1024; above it as 3); 3 = pg_tree_nj's per-join launches, one replicate
+ * after another.  The result is the same at any value. */
+#define PG_TUNE_BOOT_FORM 34
 int pg_tune(pg_ctx* ctx, int what, int64_t value);
 
 /* Device bytes the library's buffers hold in this process now (peak == 0)

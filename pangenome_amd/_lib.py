@@ -47,6 +47,8 @@ PG_TUNE_ALIGN_BAND = 29         # pg_region_align: 1 = the pairs above the cells
 PG_TUNE_ALIGN_BAND_CELLS = 30   # the band form: a pair is given up before a band of more cells than this (0 = 2^26)
 PG_TUNE_ALIGN_BAND_T0 = 31      # the band form: the first threshold, doubled until it holds the distance (0 = 64)
 PG_TUNE_NJ_BLOCKS = 32          # pg_tree_nj: blocks of the arg-min pass (0 = by size); the result is the same at any value
+PG_TUNE_BOOT_SCRATCH = 33       # pg_tree_bootstrap: device bytes of a batch of replicates (0 = 256 MiB); the result is the same
+PG_TUNE_BOOT_FORM = 34          # pg_tree_bootstrap's NJ: 0 by size and replicates, 1 LDS (n <= 128), 2 global scratch (n <= 1024), 3 per-join launches
 
 
 class PgStats(C.Structure):
@@ -128,6 +130,11 @@ SIGNATURES = {
     "pg_tree_joins": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64]),
     "pg_tree_root": (C.c_int, [_P, C.POINTER(C.c_uint32), _P, _P]),
     "pg_tree_time": (C.c_int, [_P, C.POINTER(C.c_double), _U64P]),
+    "pg_tree_bootstrap": (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, _P, C.c_uint64]),
+    "pg_tree_support": (C.c_int, [_P, _P, C.c_uint64, C.POINTER(C.c_uint32)]),
+    "pg_tree_bootstrap_joins": (C.c_int, [_P, _P, _P, C.c_uint64]),
+    "pg_tree_bootstrap_time": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _U64P]),
+    "pg_tree_bootstrap_form": (C.c_int, [_P, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]),
     "pg_region_graph": (C.c_int, [_P, _P, C.c_uint64, _P, C.c_uint64, C.c_uint32, _U64P, _U64P, _U64P, _U64P]),
     "pg_region_nodes": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_uint64]),
     "pg_region_links": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64]),
@@ -898,6 +905,62 @@ class Context:
         ms, n = C.c_double(), C.c_uint64()
         check(self.lib.pg_tree_time(self.h, C.byref(ms), C.byref(n)), "pg_tree_time")
         return ms.value, n.value
+
+    # ---------------------------------------------------- tree support
+    def tree_bootstrap(self, n_reps: int, seed: int, bits=None, n_groups=None, rep_dist: bool = False):
+        """Bootstrap support (pg_tree_bootstrap) for the joins of the last
+        tree_nj() over the last freq()'s table where it lies on the device
+        (bits None; n_groups defaults to the tree's leaves) or over host
+        presence bits [L, W].  The support and the replicate joins stay in the
+        context (tree_support / tree_bootstrap_joins).  rep_dist: return the
+        replicate matrices, uint64 [n_reps, n, n] (for tests)."""
+        G = int(getattr(self, "tree_n", 0) if n_groups is None else n_groups)
+        b, L = None, 0
+        if bits is not None:
+            b = np.ascontiguousarray(bits, dtype=np.uint64)
+            L = b.shape[0]
+            b = b.reshape(L, (G + 63) // 64)
+            if not b.size:
+                b = np.zeros(1, np.uint64)           # (NULL would mean the device table)
+        rd = np.zeros((int(n_reps), G, G), np.uint64) if rep_dist else None
+        check(self.lib.pg_tree_bootstrap(self.h, ptr(b), L, G, int(n_reps), int(seed) & (2 ** 64 - 1),
+                                         ptr(rd) if rd is not None and rd.size else None, 0 if rd is None else rd.size),
+              "pg_tree_bootstrap")
+        self.boot_reps_n, self.boot_joins_n = int(n_reps), max(G - 3, 0)
+        return rd
+
+    def tree_support(self):
+        """(support uint32 [J], replicates): the replicates whose tree has
+        each join's split (pg_tree_support)."""
+        J = getattr(self, "boot_joins_n", 0)
+        s, r = np.zeros(J, np.uint32), C.c_uint32()
+        check(self.lib.pg_tree_support(self.h, ptr(s) if J else None, J, C.byref(r)), "pg_tree_support")
+        return s, r.value
+
+    def tree_bootstrap_joins(self):
+        """(left, right), uint32 [R, J]: every replicate tree's joins
+        (pg_tree_bootstrap_joins)."""
+        R, J = getattr(self, "boot_reps_n", 0), getattr(self, "boot_joins_n", 0)
+        a, b = np.zeros((R, J), np.uint32), np.zeros((R, J), np.uint32)
+        check(self.lib.pg_tree_bootstrap_joins(self.h, ptr(a) if a.size else None, ptr(b) if b.size else None, R * J),
+              "pg_tree_bootstrap_joins")
+        return a, b
+
+    def tree_bootstrap_time(self):
+        """(ms_dist, ms_nj, ms_support, cells) of the last tree_bootstrap()
+        (pg_tree_bootstrap_time)."""
+        a, b, d, n = C.c_double(), C.c_double(), C.c_double(), C.c_uint64()
+        check(self.lib.pg_tree_bootstrap_time(self.h, C.byref(a), C.byref(b), C.byref(d), C.byref(n)),
+              "pg_tree_bootstrap_time")
+        return a.value, b.value, d.value, n.value
+
+    def tree_bootstrap_form(self):
+        """(form, batches): which form of the neighbour joining the last
+        tree_bootstrap() ran (1 LDS, 2 global scratch, 3 per-join launches, 0
+        no join) and in how many batches (pg_tree_bootstrap_form)."""
+        f, n = C.c_uint32(), C.c_uint32()
+        check(self.lib.pg_tree_bootstrap_form(self.h, C.byref(f), C.byref(n)), "pg_tree_bootstrap_form")
+        return f.value, n.value
 
     # ---------------------------------------------------- region graph
     def region_graph(self, rec_group, n_groups: int, rows=None):

@@ -112,6 +112,7 @@ void pg_destroy(pg_ctx* x) {
   c.t6.destroy();
   c.t_rs.destroy();
   c.t_nj.destroy();
+  for (auto& t : c.t_bt) t.destroy();
   for (auto& e : c.ev)
     if (e) (void)hipEventDestroy(e);
   for (auto e : c.cev)
@@ -440,6 +441,14 @@ int pg_tune(pg_ctx* x, int what, int64_t value) {
       case PG_TUNE_NJ_BLOCKS:
         if (value < 0 || value > 4096) throw pg::Error(PG_EINVAL, "pg_tune: arg-min blocks must be in [0, 4096]");
         x->c.nj_blocks = (int)value;
+        break;
+      case PG_TUNE_BOOT_SCRATCH:
+        if (value < 0) throw pg::Error(PG_EINVAL, "pg_tune: bootstrap scratch bytes must be >= 0");
+        x->c.bt_scratch = (uint64_t)value;
+        break;
+      case PG_TUNE_BOOT_FORM:
+        if (value < 0 || value > 3) throw pg::Error(PG_EINVAL, "pg_tune: bootstrap form must be 0, 1, 2 or 3");
+        x->c.bt_form_tune = (int)value;
         break;
       default:
         throw pg::Error(PG_EINVAL, "pg_tune: unknown parameter " + std::to_string(what));
@@ -940,6 +949,43 @@ int pg_tree_time(pg_ctx* x, double* ms, uint64_t* cells) {
   return guard([&] {
     if (!x) throw pg::Error(PG_EINVAL, "pg_tree_time: ctx is NULL");
     pg::tree_time(x->c, ms, cells);
+  });
+}
+
+int pg_tree_bootstrap(pg_ctx* x, const uint64_t* bits, uint64_t n_labels, uint32_t n_groups, uint32_t n_reps,
+                      uint64_t seed, uint64_t* rep_dist, uint64_t rep_dist_cap) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_tree_bootstrap: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::tree_bootstrap(x->c, bits, n_labels, n_groups, n_reps, seed, rep_dist, rep_dist_cap);
+  });
+}
+
+int pg_tree_support(pg_ctx* x, uint32_t* support, uint64_t cap, uint32_t* n_reps) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_tree_support: ctx is NULL");
+    pg::tree_support(x->c, support, cap, n_reps);
+  });
+}
+
+int pg_tree_bootstrap_joins(pg_ctx* x, uint32_t* left, uint32_t* right, uint64_t cap) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_tree_bootstrap_joins: ctx is NULL");
+    pg::tree_bootstrap_joins(x->c, left, right, cap);
+  });
+}
+
+int pg_tree_bootstrap_time(pg_ctx* x, double* ms_dist, double* ms_nj, double* ms_support, uint64_t* cells) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_tree_bootstrap_time: ctx is NULL");
+    pg::tree_bootstrap_time(x->c, ms_dist, ms_nj, ms_support, cells);
+  });
+}
+
+int pg_tree_bootstrap_form(pg_ctx* x, uint32_t* form, uint32_t* n_batches) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_tree_bootstrap_form: ctx is NULL");
+    pg::tree_bootstrap_form(x->c, form, n_batches);
   });
 }
 

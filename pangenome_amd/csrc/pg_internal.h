@@ -335,6 +335,16 @@ struct Ctx {
   double ms_nj = 0;
   uint64_t nj_cells = 0;          // the sum of m^2 over its joins
   int nj_blocks = 0;              // pg_tune: blocks of the arg-min pass (0 = by size)
+  // ---- tree support (pg_boot.hip): the result of the last pg_tree_bootstrap (a successful pg_tree_nj drops it)
+  std::vector<uint32_t> bt_support;  // [J]: the replicates whose tree has the rated tree's join t's split
+  std::vector<uint32_t> bt_join;     // [2][R][J]: left, right node of every replicate's joins
+  uint32_t bt_reps = 0, bt_form = 0, bt_batches = 0;   // (form: which NJ ran, 1 LDS, 2 global scratch, 3 per-join launches)
+  bool bt_ready = false;
+  Timer t_bt[3];                  // distances, joins, clades and matching of a batch
+  double ms_bt[3] = {0, 0, 0};    // their sums over the batches of the last pg_tree_bootstrap
+  uint64_t bt_cells = 0;          // R x the sum of m^2 over a tree's joins
+  uint64_t bt_scratch = 0;        // pg_tune: device bytes of a batch of replicates (0 = default)
+  int bt_form_tune = 0;           // pg_tune: 0 = by size, 1 = LDS where legal, 2 = global scratch, 3 = per-join launches
   // ---- region graph (pg_region.hip): the result of the last pg_region_graph
   DevBuf rg_nodes;                // [n] label, rows, max length; uint32 [n] links out, links in
   DevBuf rg_links;                // [n] from, to, count; uint32 [n] genomes
@@ -575,6 +585,12 @@ void tree_dist(Ctx& c, uint64_t* dist, uint64_t cap);
 void tree_joins(Ctx& c, uint32_t* left, uint32_t* right, uint64_t* left_len, uint64_t* right_len, uint64_t cap);
 void tree_root(Ctx& c, uint32_t* n_children, uint32_t* child, uint64_t* len);
 void tree_time(Ctx& c, double* ms, uint64_t* cells);
+void tree_bootstrap(Ctx& c, const uint64_t* h_bits, uint64_t n_labels, uint32_t n_groups, uint32_t n_reps, uint64_t seed,
+                    uint64_t* rep_dist, uint64_t rep_dist_cap);
+void tree_support(Ctx& c, uint32_t* support, uint64_t cap, uint32_t* n_reps);
+void tree_bootstrap_joins(Ctx& c, uint32_t* left, uint32_t* right, uint64_t cap);
+void tree_bootstrap_time(Ctx& c, double* ms_dist, double* ms_nj, double* ms_support, uint64_t* cells);
+void tree_bootstrap_form(Ctx& c, uint32_t* form, uint32_t* n_batches);
 
 // pg_region.hip: the front end the passes over the region rows share (pg_freq, pg_region_graph,
 // pg_region_seqs; device side in pg_region.h)

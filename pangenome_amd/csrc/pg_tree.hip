@@ -40,39 +40,13 @@
 #include <cstring>
 #include <vector>
 
-#include "pg_prim.h"
+#include "pg_tree.h"
 
 namespace pg {
 
-#define NJ_MAX_N 16384u
-#define NJ_S 16                    // fractional bits
-#define NJ_WAVES (RG_BLOCK / 64)
 #define NJ_UNROLL 4                // row words in flight per lane
-#define NJ_NONE_Q 0x7fffffffffffffffll
-#define NJ_NONE_IJ (~0ull)
 #define NJ_TILE 64
 
-typedef long long ll;
-
-struct NjKey {
-  ll q;
-  ull ij;                          // i << 32 | j
-};
-
-// (Q, i, j) < (Q2, i2, j2): the smallest Q, then the smallest i, then the smallest j
-__device__ __forceinline__ bool nj_less(ll q, ull ij, ll q2, ull ij2) { return q < q2 || (q == q2 && ij < ij2); }
-// the wave's minimum in every lane
-__device__ __forceinline__ void nj_wave_min(ll& q, ull& ij) {
-#pragma unroll
-  for (int d = 32; d; d >>= 1) {
-    const ll q2 = __shfl_xor(q, d);
-    const ull ij2 = __shfl_xor(ij, d);
-    if (nj_less(q2, ij2, q, ij)) {
-      q = q2;
-      ij = ij2;
-    }
-  }
-}
 // the block's minimum in thread 0
 __device__ __forceinline__ void nj_block_min(ll& q, ull& ij) {
   __shared__ ll sq[NJ_WAVES];
@@ -411,6 +385,7 @@ void tree_nj(Ctx& c, const uint64_t* h_dist, uint32_t n, uint64_t* n_joins) {
   c.nj_rlen.swap(h_rlen);
   c.nj_n = n;
   c.nj_ready = true;
+  c.bt_ready = false;                                      // (the support described the old tree)
   if (n_joins) *n_joins = J;
 }
 

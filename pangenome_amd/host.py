@@ -1165,13 +1165,19 @@ def tree_name_text(name) -> bytes:
     return nm
 
 
-def tree_newick(names, joins, root) -> bytes:
+def tree_newick(names, joins, root, support=None) -> bytes:
     """The Newick text of tree_nj's (or the device's) tables over the leaves
     called names: `(<child>:<len>,<child>:<len>,<child>:<len>);` and a line
-    feed, nested, each join's left child before its right.  No leaf: empty."""
+    feed, nested, each join's left child before its right.  No leaf: empty.
+    support: None, or (counts [J], replicates) of tree_bootstrap - every
+    join's closing parenthesis is then followed by floor(100 * count /
+    replicates) as the node's label; the root's carries none."""
     n = len(names)
     if not n:
         return b""
+    pct = None
+    if support is not None:
+        pct = [b"%d" % (100 * int(s) // int(support[1])) for s in support[0]]
     left, right = [int(x) for x in joins["left"]], [int(x) for x in joins["right"]]
     ll, rl = [int(x) for x in joins["left_len"]], [int(x) for x in joins["right_len"]]
     out = []
@@ -1190,7 +1196,7 @@ def tree_newick(names, joins, root) -> bytes:
             out.append(tree_name_text(names[x]))
         else:
             t = x - n
-            stack.append(b":" + tree_len_text(rl[t]) + b")")
+            stack.append(b":" + tree_len_text(rl[t]) + b")" + (pct[t] if pct else b""))
             stack.append(right[t])
             stack.append(b":" + tree_len_text(ll[t]) + b",")
             stack.append(left[t])
@@ -1235,6 +1241,135 @@ def write_tree_files(prefix: str, names, dist, joins, root, var: bool = False) -
         left_len=np.asarray(joins["left_len"], _U64), right_len=np.asarray(joins["right_len"], _U64),
         root_child=np.asarray(root[0], np.uint32), root_len=np.asarray(root[1], _U64),
         frac_bits=np.int64(TREE_FRAC_BITS)))
+
+
+# --------------------------------------------------------------- tree support
+BOOT_MAX_REPS = 4096
+BOOT_MAX_LABELS = 1 << 31
+
+
+def boot_index(x, L: int) -> np.ndarray:
+    """idx = ((x >> 32) * L) >> 32 of 64-bit outputs x, in unsigned 64 bits:
+    in [0, L), and the product does not wrap while L <= 2^31."""
+    L = int(L)
+    if not 0 <= L <= BOOT_MAX_LABELS:
+        raise ValueError("boot_index: %d labels, at most 2^31" % L)
+    return ((np.asarray(x, _U64) >> _U64(32)) * _U64(L)) >> _U64(32)
+
+
+def boot_draws(seed: int, b: int, L: int) -> np.ndarray:
+    """Replicate b's drawn rows, uint64 [L]: idx(b, t) = boot_index of output
+    t of synth.splitmix64(seed, b + 1, L)."""
+    from . import synth
+    return boot_index(synth.splitmix64(int(seed), int(b) + 1, int(L)), L)
+
+
+def tree_splits(joins, n: int) -> list:
+    """The split of every join of a tree over n leaves, as Python integers
+    (bit g = genome g): the join's clade - a leaf's is itself, a node's the
+    union of its children's - if leaf 0 is not in it, otherwise the
+    complement within 0 .. n - 1."""
+    left, right = [int(x) for x in joins["left"]], [int(x) for x in joins["right"]]
+    full = (1 << n) - 1
+    clade = [1 << i for i in range(n)]
+    out = []
+    for a, b in zip(left, right):
+        c = clade[a] | clade[b]
+        clade.append(c)
+        out.append(full ^ c if c & 1 else c)
+    return out
+
+
+def tree_clade_sizes(joins, n: int) -> list:
+    """The number of leaves below every join (its clade, not its split)."""
+    size = [1] * n
+    for a, b in zip(joins["left"], joins["right"]):
+        size.append(size[int(a)] + size[int(b)])
+    return size[n:]
+
+
+def tree_bootstrap(bits, n_groups: int, joins, n_reps: int, seed: int, dist=None, rep_dist: bool = False) -> dict:
+    """Tree support's specification (pg_tree_bootstrap computes the same on
+    the device; include/pangenome.h, "tree support", has the definition).
+    bits: uint64 [L, W] presence words; joins: the rated tree's (tree_nj's
+    dict, or the device's); n_reps in [1, 4096].  dist: None, or the matrix
+    the rated tree was built from - ValueError if it is not the Hamming
+    matrix of bits (the guard).  Returns support uint32 [J] (the replicates
+    whose tree has join t's split), rep_left and rep_right uint32 [R, J] (the
+    replicate trees' joins) and, asked for, rep_dist uint64 [R, n, n].
+    A replicate's matrix: with c[l] = how often row l was drawn and u the 0 / 1
+    table, s = u^T diag(c) u in float64 (exact: sums at most 2^31) and
+    d(g, h) = s[g][g] + s[h][h] - 2 s[g][h]."""
+    G, R = int(n_groups), int(n_reps)
+    W = (G + 63) // 64
+    b = np.ascontiguousarray(bits, dtype=_U64)
+    L = b.shape[0]
+    b = b.reshape(L, W)
+    if not 1 <= R <= BOOT_MAX_REPS:
+        raise ValueError("tree_bootstrap: %d replicates: 1 to %d" % (R, BOOT_MAX_REPS))
+    if L > BOOT_MAX_LABELS:
+        raise ValueError("tree_bootstrap: %d labels, at most 2^31" % L)
+    if G & 63 and L and (b[:, W - 1] >> _U64(G & 63)).any():
+        raise ValueError("tree_bootstrap: a row has a bit at or above genome %d" % G)
+    J = max(G - 3, 0)
+    if len(joins["left"]) != J:
+        raise ValueError("tree_bootstrap: the tree has %d joins, %d genomes have %d" % (len(joins["left"]), G, J))
+    u = np.unpackbits(b.view(np.uint8).reshape(L, W * 8), axis=1, bitorder="little")[:, :G].astype(np.float64)
+
+    def hamming(count):
+        s = (u * count[:, None]).T @ u
+        dg = np.diag(s)
+        return (dg[:, None] + dg[None, :] - 2 * s).astype(_U64)
+    if dist is not None and not np.array_equal(hamming(np.ones(L)), np.asarray(dist, _U64).reshape(G, G)):
+        raise ValueError("tree_bootstrap: the tree was not built from this table")
+    where = {}
+    for t, s in enumerate(tree_splits(joins, G)):
+        where[s] = t
+    out = {"support": np.zeros(J, np.uint32), "rep_left": np.zeros((R, J), np.uint32),
+           "rep_right": np.zeros((R, J), np.uint32)}
+    if rep_dist:
+        out["rep_dist"] = np.zeros((R, G, G), _U64)
+    for r in range(R):
+        count = np.bincount(boot_draws(seed, r, L).astype(np.int64), minlength=L).astype(np.float64)
+        d = hamming(count)
+        if rep_dist:
+            out["rep_dist"][r] = d
+        rj, _ = tree_nj(d)
+        out["rep_left"][r], out["rep_right"][r] = rj["left"], rj["right"]
+        for s in tree_splits(rj, G):
+            if s in where:
+                out["support"][where[s]] += 1
+    return out
+
+
+def write_tree_support_files(prefix: str, names, joins, root, boot: dict, seed: int, var: bool = False) -> None:
+    """The `-B` files of `prefix`: `_fr_tree_support.nwk` (`_fr_tree.nwk` with
+    every join's support as an integer percentage behind its closing
+    parenthesis), `_fr_tree_support.tsv` (per join its node, the raw count,
+    the replicates and the clade's leaves) and `_fr_tree_boot.npz`; var: the
+    tree of the differences, `_fr_vartree_support.nwk` and `.tsv` alone.  boot:
+    tree_bootstrap's dict (or the device's).  Each is written to `.tmp` and
+    renamed when whole."""
+    nm = [bytes(x) for x in names]
+    n = len(nm)
+    sup = np.asarray(boot["support"], np.uint32)
+    R = int(np.asarray(boot["rep_left"]).shape[0])
+    stem = "_fr_vartree_support" if var else "_fr_tree_support"
+
+    def whole(suffix, fill):
+        fn = prefix + suffix
+        with open(fn + ".tmp", "wb") as f:
+            fill(f)
+        os.replace(fn + ".tmp", fn)
+    whole(stem + ".nwk", lambda f: f.write(tree_newick(nm, joins, root, support=(sup, R))))
+    whole(stem + ".tsv", lambda f: f.write(b"#node\tsupport\treplicates\tleaves\n" + b"".join(
+        b"%d\t%d\t%d\t%d\n" % (n + t, int(s), R, k) for t, (s, k) in enumerate(zip(sup, tree_clade_sizes(joins, n))))))
+    if var:
+        return
+    gn = np.array(nm, dtype=np.bytes_) if nm else np.zeros(0, "S1")
+    whole("_fr_tree_boot.npz", lambda f: np.savez(
+        f, genomes=gn, support=sup, replicates=np.int64(R), seed=np.uint64(seed),
+        rep_left=np.asarray(boot["rep_left"], np.uint32), rep_right=np.asarray(boot["rep_right"], np.uint32)))
 
 
 REGION_COLS = (("labels", np.int64), ("rows", np.uint64), ("max_len", np.uint64), ("n_out", np.uint32),

@@ -258,7 +258,7 @@ def rdbg_edges(g: DeviceGraph, Ns, chunk, rc, brkpt="", keep_on_device=False):
 def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_dict=None, saved=None,
               hashfunc=None, jit=True, chunk=2 ** 33, rc=False, cluster=True, out=None, min_weight=1, groups=None,
               orders=0, links=False, seqs=False, inflation2=3, sites=False, bubbles=0, variants="", align=False,
-              align_band=False, tree=False):
+              align_band=False, tree=False, boot=0):
     """:1853-1951: edge weights -> `<qry>_rdbg_weight.xyz` -> mcl (or reuse)
     -> label dictionary -> print the region rows.  The edges, the label
     table, the rows and both texts are made on the device; the host writes
@@ -305,7 +305,11 @@ def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_
     (pg_freq_compare with no orders is run first if orders has not) and
     `<qry>_fr_dist.tsv`, `_fr_tree.nwk`, `_fr_tree.tsv` and `_fr_tree.npz`
     written; with align as well, a second tree from the primitive VCF lines'
-    carrier bits as `<qry>_fr_vartree.nwk` and `_fr_vardist.tsv`."""
+    carrier bits as `<qry>_fr_vartree.nwk` and `_fr_vardist.tsv`.  boot (-B,
+    with tree): that many bootstrap replicates rate every join of each tree
+    (pg_tree_bootstrap) right after its files, as `<qry>_fr_tree_support.nwk`,
+    `_fr_tree_support.tsv` and `_fr_tree_boot.npz`, and for the second tree
+    `_fr_vartree_support.nwk` and `_fr_vartree_support.tsv`."""
     out = out or sys.stdout
     g = rdbg_dict
     res = rdbg_edges(g, Ns, chunk, rc, brkpt=brkpt, keep_on_device=True)
@@ -377,7 +381,7 @@ def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_
         if orders:
             write_compare(g, qry, gnames, int(orders))
         if tree:
-            write_tree(g, qry, gnames, compared=bool(orders))
+            write_tree(g, qry, gnames, compared=bool(orders), boot=int(boot))
         if links:
             write_region(g, qry, names, flags, groups)
         if seqs:
@@ -391,7 +395,7 @@ def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_
                 if align:
                     write_align(g, qry, names, flags, groups, variants, bool(align_band))
                     if tree:
-                        write_var_tree(g, qry, gnames)
+                        write_var_tree(g, qry, gnames, boot=int(boot))
     gen = g.ctx.label_gen
     return LabelTable(loader=lambda: g.ctx.labels(gen))           # (raises once a later label pass replaced it)
 
@@ -448,18 +452,35 @@ def write_compare(g, qry, gnames, n_orders):
     host.write_compare_files(qry, gnames, g.ctx.freq_shared(), orders, pan, core)
 
 
-def write_tree(g, qry, gnames, compared):
+def write_tree(g, qry, gnames, compared, boot=0):
     """-T: the neighbour-joining tree of the genomes (pg_tree_nj) from the
     shared matrix of the comparison where it lies on the device - write_compare's
     (compared), or one made here over no orders - as `<qry>_fr_dist.tsv`,
-    `_fr_tree.nwk`, `_fr_tree.tsv` and `_fr_tree.npz`."""
+    `_fr_tree.nwk`, `_fr_tree.tsv` and `_fr_tree.npz`.  boot (-B): then its
+    joins rated by that many bootstrap replicates over the frequency table
+    where it still lies on the device (write_tree_support)."""
     if not compared:
         g.ctx.freq_compare(None)
     g.ctx.tree_nj()
-    host.write_tree_files(qry, gnames, g.ctx.tree_dist(), g.ctx.tree_joins(), g.ctx.tree_root())
+    joins, root = g.ctx.tree_joins(), g.ctx.tree_root()
+    host.write_tree_files(qry, gnames, g.ctx.tree_dist(), joins, root)
+    if boot:
+        write_tree_support(g, qry, gnames, joins, root, boot)
 
 
-def write_var_tree(g, qry, gnames):
+def write_tree_support(g, qry, gnames, joins, root, boot, bits=None):
+    """-B: the tree just built rated by `boot` bootstrap replicates
+    (pg_tree_bootstrap, seed synth.DEFAULT_SEED) over the device's frequency
+    table (bits None) or the host rows the tree of the differences came from,
+    as host.write_tree_support_files' files."""
+    from . import synth
+    g.ctx.tree_bootstrap(boot, synth.DEFAULT_SEED, bits=bits, n_groups=len(gnames))
+    left, right = g.ctx.tree_bootstrap_joins()
+    res = {"support": g.ctx.tree_support()[0], "rep_left": left, "rep_right": right}
+    host.write_tree_support_files(qry, gnames, joins, root, res, synth.DEFAULT_SEED, var=bits is not None)
+
+
+def write_var_tree(g, qry, gnames, boot=0):
     """-T with -A: a second tree, from the differences: the carrier bits of
     the primitive VCF lines just written (write_align) compared as presence
     rows (pg_freq_compare, no orders; this replaces the device's comparison,
@@ -467,9 +488,13 @@ def write_var_tree(g, qry, gnames):
     one of the two genomes - a genome with no allele at a site carries none of
     its lines - as `<qry>_fr_vartree.nwk` and `_fr_vardist.tsv`."""
     G = len(gnames)
-    g.ctx.freq_compare(None, bits=g.ctx.region_align_lines(G)["bits"], n_groups=G)
+    bits = g.ctx.region_align_lines(G)["bits"]
+    g.ctx.freq_compare(None, bits=bits, n_groups=G)
     g.ctx.tree_nj()
-    host.write_tree_files(qry, gnames, g.ctx.tree_dist(), g.ctx.tree_joins(), g.ctx.tree_root(), var=True)
+    joins, root = g.ctx.tree_joins(), g.ctx.tree_root()
+    host.write_tree_files(qry, gnames, g.ctx.tree_dist(), joins, root, var=True)
+    if boot:
+        write_tree_support(g, qry, gnames, joins, root, boot, bits=bits)
 
 
 def write_region(g, qry, names, flags, groups):
@@ -629,6 +654,10 @@ def manual_print(out=None):
                  "  -T: with -g, a neighbour-joining tree of the genomes from the regions they share. 0 (off) or 1; single process only.",
                  "      writes <in>_fr_dist.tsv, _fr_tree.nwk (Newick), _fr_tree.tsv, _fr_tree.npz and, with -A 1, a second tree from",
                  "      the primitive VCF lines: <in>_fr_vartree.nwk, _fr_vardist.tsv",
+                 "  -B: with -T 1, bootstrap support for the tree's branches from this many replicates (0: off, at most 4096): the regions",
+                 "      are resampled and every branch rated by the share of replicate trees that split the genomes the same way. single",
+                 "      process only. writes <in>_fr_tree_support.nwk (Newick, percentages as node labels), _fr_tree_support.tsv,",
+                 "      _fr_tree_boot.npz and, with -A 1, <in>_fr_vartree_support.nwk, _fr_vartree_support.tsv",
                  "  -D: the reduced de bruijn graph", "  -R: break point of reduced de bruijn graph",
                  "  -v: with -g, the variable sites: pairs of regions joined in two or more ways, directly or through one region.",
                  "      0 (off) or 1; single process only. writes <in>_fr_sites.tsv, _fr_sites_genomes.tsv, _fr_sites.npz",
@@ -658,7 +687,7 @@ def parse_args(argv):
     """:1983-1997 — same flag handling, including `-k27` and skipped unknowns."""
     args = {"-i": "", "-k": "50", "-n": "2**63", "-r": "", "-d": "", "-R": "", "-D": "", "-c": "2", "-a": "mcl",
             "-w": "1", "-g": "", "-p": "0", "-l": "0", "-s": "0", "-I": "1.5", "-v": "0", "-b": "0",
-            "-V": "", "-A": "0", "-L": "0", "-T": "0"}
+            "-V": "", "-A": "0", "-L": "0", "-T": "0", "-B": "0"}
     N = len(argv)
     for i in range(1, N):
         k = argv[i]
@@ -774,6 +803,16 @@ def tree_arg(args):
     return None if args["-T"] == "1" and not args["-g"] else args["-T"] == "1"
 
 
+def boot_arg(args, tree):
+    """-B's value: the bootstrap replicates (0: off), or None for a value that
+    is refused - not a decimal integer in [0, 4096], or >= 1 without an
+    accepted -T 1."""
+    if not args["-B"].isascii() or not args["-B"].isdigit() or int(args["-B"]) > host.BOOT_MAX_REPS:
+        return None
+    b = int(args["-B"])
+    return None if b and not tree else b
+
+
 def entry_point(argv, out=None, device=0):
     out = out or sys.stdout
     args = parse_args(argv)
@@ -785,7 +824,8 @@ def entry_point(argv, out=None, device=0):
     align = align_arg(args, variants)
     band = band_arg(args, align)
     tree = tree_arg(args)
-    bad = (tree is None or not qry or n_orders is None or links is None or seqs is None or sites is None or bubbles is None or
+    boot = boot_arg(args, tree)
+    bad = (tree is None or boot is None or not qry or n_orders is None or links is None or seqs is None or sites is None or bubbles is None or
            variants is None or align is None or band is None)
     clu = None if bad else cluster_args(args)
     if clu is None:
@@ -812,6 +852,8 @@ def entry_point(argv, out=None, device=0):
         clu["align_band"] = True
     if tree:
         clu["tree"] = True
+    if boot:
+        clu["boot"] = boot
     # a group file, and -V's genome, are checked against the records before anything is built
     chk = (lambda g: check_groups(g, Ns, grp, variants)) if grp and (grp != "record" or variants) else None
     chunk = 2 ** 33
