@@ -92,7 +92,7 @@ void pg_destroy(pg_ctx* x) {
   pg::DevBuf* bufs[] = {&c.fasta_own, &c.span_sum, &c.span_start, &c.n_sel, &c.rec_start, &c.rec_len,
                         &c.rec_hdr, &c.rec_ptr, &c.rec_flag, &c.cls, &c.p2, &c.e16, &c.scratch, &c.table, &c.ovf, &c.flags,
                         &c.recA_key, &c.recA_mw, &c.ctrA, &c.recS_key[0], &c.recS_key[1], &c.recS_mw[0],
-                        &c.recS_mw[1], &c.ctrS, &c.snapA, &c.rseg, &c.k5_ctr, &c.tile_sched, &c.tile_desc, &c.k3_queue,
+                        &c.recS_mw[1], &c.ctrS, &c.snapA, &c.rseg, &c.k5_ctr, &c.tile_sched, &c.tile_desc, &c.tile_geo, &c.k3_queue,
                         &c.k3_hint, &c.part_cnt, &c.tile_cnt, &c.tile_off, &c.occ, &c.edge_tab, &c.pair_tab,
                         &c.edge_out, &c.edge_exp, &c.lab_tab, &c.lab_list, &c.rows_buf, &c.xyz_off,
                         &c.text_buf, &c.clu_text, &c.mk_mat, &c.fr_tab, &c.fr_spec, &c.fr_grp, &c.fr_text,

@@ -607,6 +607,14 @@ __device__ __forceinline__ Stage stage_of(const TileDesc& td, int k, bool dedup,
   return g;
 }
 
+// Search geometry of one (member, reference, anchor) triple, computed once
+// per block in the staging phase: ibhi = the reference index of drift 0's
+// candidate + DRIFT; [lo, hi] the full search range, [lo1, hi1] its part
+// within the hint window (empty if the triple does not dedup).
+struct TriGeo {
+  int ibhi, lo, hi, lo1, hi1;
+};
+
 // tiles [t, te) of XCD x in chunk c of nch (host and device)
 // (a chunk is the fraction [b0, b1) / bt of every XCD's eighth)
 __host__ __device__ __forceinline__ void xcd_chunk(uint64_t ntiles, uint32_t b0, uint32_t b1, uint32_t bt, uint64_t x,
@@ -1115,13 +1123,55 @@ k_cover_q(const uint8_t* __restrict__ cls, uint64_t ncls, const TileDesc* __rest
 
 #endif  // PG_COVER_LEGACY
 
-// Search geometry of one (member, reference, anchor) triple, computed once
-// per block in the staging phase: ibhi = the reference index of drift 0's
-// candidate + DRIFT; [lo, hi] the full search range, [lo1, hi1] its part
-// within the hint window (empty if the triple does not dedup).
-struct TriGeo {
-  int ibhi, lo, hi, lo1, hi1;
+// A coverage group's geometry for the packed pass, written once per group by
+// k_tiles beside its TileDescs: everything k_cover_p used to derive per wave
+// from the descriptors, the two reference records and k.  All of it is
+// block-uniform; what depends on the XCD's hints or on the search stays in
+// the kernel.  Positions are relative to the stripe base qt and fit 32 bits
+// (clamp30 where a record's length could carry them out of range: only the
+// side of a comparison with a window index in [0, TILE) matters there).
+// A wave reads the header and its own member (mem[wave]) with scalar loads;
+// the one-lane-per-anchor / per-triple phases read theirs with vector loads.
+// The anchors' and triples' values are affine in the anchor index, so the
+// descriptor holds their base and limits and does not depend on the number
+// of anchors (PG_TUNE_K3_ANCHORS).
+struct RefSpan {                  // a reference's staged span of the stripe (32 B)
+  long long rd0;                  // first staged p2 word (s_ref word RPADW)
+  int rnw;                        // staged words
+  int ph;                         // drift sets: last covered window + IW - 1 at drift 0 (min(rfn, phi) - k - IW - qt)
+  int ibhi0, lomin, himax;        // search, s_ref base indices: anchor 0's ibhi; lo >= lomin; hi <= himax
+  int pl;                         // drift sets: first covered window at drift 0 (max(plo + 1, 1) - qt)
 };
+struct MemberGeo {                // one member tile (48 B)
+  long long rs, last;             // the record's compacted start, its last window (rn - k): the WorkItem's
+  long long wb;                   // p2 word of record position qt - 1: (rs + qt - 1) >> 4
+  int r;                          // the record, -1: an empty slot
+  int sh2;                        // 2 * ((rs + qt - 1) & 15): bit shift of position qt - 1 in word wb
+  int lastrel;                    // last - qt
+  int arel;                       // rn - qt - 8 - ALEN: anchor ai lies in the record iff ai * astep <= arel
+  int U0[2];                      // per reference: s_ref base index of the member's word-grid base at drift 0
+};
+struct alignas(16) GroupGeo {
+  long long qt;                   // the stripe base
+  uint32_t bits;                  // live | dm0 << 8 | dm1 << 16, one bit per member
+  uint32_t pad;
+  RefSpan ref[2];
+  MemberGeo mem[QM];
+};
+static_assert(QM <= 8 && sizeof(RefSpan) == 32 && sizeof(MemberGeo) == 48 && sizeof(GroupGeo) == 16 + 64 + 48 * QM &&
+                  sizeof(GroupGeo) % 16 == 0,
+              "wide aligned loads of a header, a reference or a member");
+// what a hint / drift-set lane needs of its triple's member and reference (staged by the triple's geometry lane)
+struct HintGeo {
+  int r, U0, pl, ph;
+};
+// A coverage launch's groups per XCD: XCD x takes [g0[x], ge[x]) (xcd_chunk, on the host)
+struct XcdBounds {
+  uint32_t g0[8], ge[8];
+};
+__host__ __device__ __forceinline__ int clamp30(long long v) {
+  return (int)(v < -(1ll << 30) ? -(1ll << 30) : v > (1ll << 30) ? (1ll << 30) : v);
+}
 
 // ---- K3 coverage pass, packed form (the default; north_star's "2-bit
 // encode ... packed base stream").  Same groups, drift search and coverage
@@ -1287,9 +1337,11 @@ __device__ __forceinline__ uint32_t even_bits(uint32_t x) {
 template <int NAP>
 __global__ void __launch_bounds__(CBLOCK, 8)
 k_cover_p(const uint32_t* __restrict__ p2, const uint8_t* __restrict__ e16, uint64_t n_p2,
-          const uint8_t* __restrict__ cls_dbg, const TileDesc* __restrict__ descs, WorkItem* __restrict__ queue, unsigned long long* __restrict__ qcount,
-          unsigned long long qcap, int k, int ref, long long rfs, long long rfn, int ref2, long long r2s,
-          long long r2n, int* __restrict__ hints, int nrec, uint64_t ngroups, uint32_t b0, uint32_t b1, uint32_t bt) {
+#ifdef PG_DEBUG_BOUNDS   // (the debug check's class bytes and the references' starts in them)
+          const uint8_t* __restrict__ cls_dbg, long long rfs, long long r2s,
+#endif
+          const GroupGeo* __restrict__ geo, WorkItem* __restrict__ queue, unsigned long long* __restrict__ qcount,
+          unsigned long long qcap, int k, int* __restrict__ hints, int nrec, XcdBounds xb) {
   static_assert(NAP >= 2 && QM * NAP + QM * 2 * NAP <= CBLOCK, "anchor loads and triple geometry: one thread each");
   constexpr int ASTEPP = astep_p<NAP>();
   __shared__ __attribute__((aligned(16))) uint32_t s_ref[2][RDW];
@@ -1299,65 +1351,54 @@ k_cover_p(const uint32_t* __restrict__ p2, const uint8_t* __restrict__ e16, uint
   __shared__ unsigned long long s_qbase;
   __shared__ Drifts2<NAP> s_dr[QM][2];
   __shared__ TriGeo s_tri[QM * 2 * NAP];
+  __shared__ HintGeo s_hg[QM * 2 * NAP];
   __shared__ uint32_t s_rexc;
-  uint64_t g, ge;
-  xcd_chunk(ngroups, b0, b1, bt, blockIdx.x & 7, g, ge);
-  g += blockIdx.x >> 3;
-  if (g >= ge) return;                             // (block-uniform, before any barrier)
+  const uint32_t xcd = blockIdx.x & 7;
+  const uint32_t g = xb.g0[xcd] + (blockIdx.x >> 3);
+  if (g >= xb.ge[xcd]) return;                     // (block-uniform, before any barrier)
   const int t = (int)threadIdx.x;
-  const long long qt = (long long)descs[QM * g].stripe * TILE;
-  // the references' spans of this stripe: [qt-1-DRIFT, qt+TILE+k+1+DRIFT) clipped, staged as the words
-  // from rd0 (s_ref word RPADW); rbase = the s_ref base index of record position 0
-  RefGeo rg[2];
-  long long rd0[2];
-  int rnw[2];
-#pragma unroll
-  for (int ri = 0; ri < 2; ++ri) {
-    const long long s = ri ? r2s : rfs, n = ri ? r2n : rfn;
-    rg[ri].plo = qt - 1 - DRIFT > 0 ? qt - 1 - DRIFT : 0;
-    rg[ri].phi = qt + TILE + k + 1 + DRIFT < n ? qt + TILE + k + 1 + DRIFT : n;
-    rg[ri].rfn = n;
-    rd0[ri] = (s + rg[ri].plo) >> 4;
-    rnw[ri] = (int)(((s + rg[ri].phi + 15) >> 4) - rd0[ri]);
-    rg[ri].rbase = 16 * RPADW + s - 16 * rd0[ri];
-  }
-  long long mrs[QM], mrn[QM];
-  uint32_t dm0 = 0, dm1 = 0, live = 0;
-#pragma unroll
-  for (int m = 0; m < QM; ++m) {
-    const TileDesc td = descs[QM * g + m];
-    mrs[m] = td.rs;
-    mrn[m] = td.rn;
-    const bool d0 = td.r >= 0 && ref >= 0 && ref != td.r;
-    live |= (uint32_t)(td.r >= 0) << m;
-    dm0 |= (uint32_t)d0 << m;
-    dm1 |= (uint32_t)(d0 && ref2 >= 0 && ref2 != td.r) << m;
-  }
+  // the group's geometry: the header and this wave's member, scalar loads
+  const GroupGeo& G = geo[g];
+  const int mw = __builtin_amdgcn_readfirstlane(t >> 6), lw = t & 63;
+  const MemberGeo& me = G.mem[mw];
+  const long long qt = G.qt;
+  const uint32_t live = G.bits & 0xFFu;
+  uint32_t dm0 = (G.bits >> 8) & 0xFFu, dm1 = (G.bits >> 16) & 0xFFu;
   // the coverage phase's member words and exception bytes, loaded now: they
   // depend on nothing the block computes, and the barriers up to that phase
   // wait for LDS only (cover_barrier), so the loads land under the search
-  const int mw = __builtin_amdgcn_readfirstlane(t >> 6), lw = t & 63;
-  uint32_t M[LW], eex = 0;
+  uint32_t M[LW], eex[3];
   {
-    long long rsm = mrs[0];
-#pragma unroll
-    for (int y = 1; y < QM; ++y) if (mw == y) rsm = mrs[y];
-    const long long wb = ((rsm + qt - 1) >> 4) + 4 * lw, a = wb & ~3ll;
+    const long long wb = me.wb + 4 * lw, a = wb & ~3ll;
     const bool on = (dm0 >> mw) & 1u;
 #pragma unroll
     for (int i = 0; i < LW; ++i) M[i] = on ? p2_word(p2, wb + i, n_p2) : 0u;
 #pragma unroll
-    for (int i = 0; i < 3; ++i)
-      if (on && a + 4 * i >= 0 && (uint64_t)(a + 4 * i + 4) <= n_p2 + 16)
-        eex |= *reinterpret_cast<const uint32_t*>(e16 + a + 4 * i);
+    for (int i = 0; i < 3; ++i)                    // (kept apart until the coverage phase: an OR here would wait for them)
+      eex[i] = on && a + 4 * i >= 0 && (uint64_t)(a + 4 * i + 4) <= n_p2 + 16
+                   ? *reinterpret_cast<const uint32_t*>(e16 + a + 4 * i) : 0u;
+  }
+  // the references' staged words and their exception bytes, two words per
+  // thread and reference: loaded now as well (their addresses come from the
+  // descriptor alone), stored to s_ref behind the first barrier
+  static_assert(RSTAGEW <= 2 * CBLOCK, "two words per thread and reference");
+  uint32_t rv[2][2], rx[2][2];
+#pragma unroll
+  for (int ri = 0; ri < 2; ++ri) {
+    const long long rd0 = G.ref[ri].rd0;
+    const int nw = (ri ? dm1 != 0 : dm0 != 0) ? G.ref[ri].rnw : 0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int i = t + h * CBLOCK;
+      rv[ri][h] = i < nw ? p2_word(p2, rd0 + i, n_p2) : 0u;
+      rx[ri][h] = i < nw && PG_BOK(rd0 + i >= 0 && (uint64_t)(rd0 + i) < n_p2, 12, rd0 + i, n_p2) ? e16[rd0 + i] : 0u;
+    }
   }
   if (t == 0) s_rexc = 0u;
   if (t < QM * NAP) {                              // anchors: 32 bases = 2 words each
     const int m = t / NAP, ai = t % NAP;
-    long long rs = mrs[0];
-#pragma unroll
-    for (int y = 1; y < QM; ++y) rs = m == y ? mrs[y] : rs;
-    const long long ga = rs + qt + 8 + (long long)ai * ASTEPP, x = ga >> 4;
+    const int ga = (G.mem[m].sh2 >> 1) + 9 + ai * ASTEPP;   // record position qt + 8 + ai * ASTEPP from word wb
+    const long long x = G.mem[m].wb + (ga >> 4);
     const uint32_t sb = 2u * (uint32_t)(ga & 15);
     uint32_t P0 = 0, P1 = 0, P2 = 0;
     if ((dm0 >> m) & 1u) { P0 = p2_word(p2, x, n_p2); P1 = p2_word(p2, x + 1, n_p2); P2 = p2_word(p2, x + 2, n_p2); }
@@ -1366,43 +1407,32 @@ k_cover_p(const uint32_t* __restrict__ p2, const uint8_t* __restrict__ e16, uint
   } else if (t >= CBLOCK - QM * 2 * NAP) {         // triples: search geometry around the XCD's hint
     const int x = t - (CBLOCK - QM * 2 * NAP), m = x / (2 * NAP), ri = (x / NAP) & 1, ai = x % NAP;
     (&s_best[0][0][0])[x] = ~0u;
-    TriGeo G{0, 0, -1, 0, -1};
+    const MemberGeo& mg = G.mem[m];
+    const RefSpan& R = G.ref[ri];
+    const int r = mg.r;
+    s_hg[x] = HintGeo{r, mg.U0[ri], R.pl, R.ph};
+    TriGeo T{0, 0, -1, 0, -1};
     if ((((ri ? dm1 : dm0) >> m) & 1u)) {
-      const TileDesc td = descs[QM * g + m];
-      const int hh = hints[(size_t)(blockIdx.x & 7) * 2 * nrec + (ri ? nrec : 0) + td.r];
+      const int hh = hints[(size_t)xcd * 2 * nrec + (ri ? nrec : 0) + r];
       const int h = hh < 0 ? DRIFT : hh;
-      const RefGeo& R = ri ? rg[1] : rg[0];
-      const long long a = qt + 8 + (long long)ai * ASTEPP;
-      G.ibhi = (int)(R.rbase + a + DRIFT);
-      G.lo = max(G.ibhi - 2 * DRIFT, (int)(R.rbase + R.plo));
-      G.hi = a + ALEN > td.rn ? -1 : min(G.ibhi, (int)(R.rbase + R.phi) - ALEN);
-      G.lo1 = max(G.lo, G.ibhi - (h + HWIN2P));
-      G.hi1 = min(G.hi, G.ibhi - (h - HWIN2P));
+      T.ibhi = R.ibhi0 + ai * ASTEPP;
+      T.lo = max(T.ibhi - 2 * DRIFT, R.lomin);
+      T.hi = ai * ASTEPP > mg.arel ? -1 : min(T.ibhi, R.himax);
+      T.lo1 = max(T.lo, T.ibhi - (h + HWIN2P));
+      T.hi1 = min(T.hi, T.ibhi - (h - HWIN2P));
     }
-    s_tri[x] = G;
+    s_tri[x] = T;
   }
   cover_barrier();                                 // (s_rexc cleared)
   {
-    static_assert(RSTAGEW <= 2 * CBLOCK, "two words per thread and reference");
-    uint32_t v[2][2], ex = 0;
-#pragma unroll
-    for (int ri = 0; ri < 2; ++ri) {
-      const int nw = (ri ? dm1 != 0 : dm0 != 0) ? rnw[ri] : 0;
-#pragma unroll
-      for (int h = 0; h < 2; ++h) {
-        const int i = t + h * CBLOCK;
-        v[ri][h] = i < nw ? p2_word(p2, rd0[ri] + i, n_p2) : 0u;
-        if (i < nw && PG_BOK(rd0[ri] + i >= 0 && (uint64_t)(rd0[ri] + i) < n_p2, 12, rd0[ri] + i, n_p2) &&
-            e16[rd0[ri] + i])
-          ex |= 1u << ri;
-      }
-    }
+    const int rnw[2] = {G.ref[0].rnw, G.ref[1].rnw};
 #pragma unroll
     for (int ri = 0; ri < 2; ++ri)
 #pragma unroll
       for (int h = 0; h < 2; ++h)
         if (t + h * CBLOCK < rnw[ri] && PG_BOK(RPADW + t + h * CBLOCK < RDW, 13, rnw[ri], t))
-          s_ref[ri][RPADW + t + h * CBLOCK] = v[ri][h];
+          s_ref[ri][RPADW + t + h * CBLOCK] = rv[ri][h];
+    const uint32_t ex = ((rx[0][0] | rx[0][1]) ? 1u : 0u) | ((rx[1][0] | rx[1][1]) ? 2u : 0u);
     if (ex) atomicOr(&s_rexc, ex);
   }
   cover_barrier();
@@ -1431,24 +1461,16 @@ k_cover_p(const uint32_t* __restrict__ p2, const uint8_t* __restrict__ e16, uint
       const bool keep = first(ai);
       bool last = b != ~0u;                         // the last anchor that found one
       for (int j = ai + 1; j < NAP; ++j) last &= B[j] == ~0u;
-      long long rs = mrs[0];
-#pragma unroll
-      for (int y = 1; y < QM; ++y) rs = m == y ? mrs[y] : rs;
-      const int r = descs[QM * g + m].r;
-      (void)PG_BOK(r >= 0 && r < nrec, 52, (long long)r, (long long)nrec);
+      const HintGeo hg = s_hg[t];
+      (void)PG_BOK(hg.r >= 0 && hg.r < nrec, 52, (long long)hg.r, (long long)nrec);
       // the hint: the drift nearest the record's next stripe
-      if (last) hints[(size_t)(blockIdx.x & 7) * 2 * nrec + (ri ? nrec : 0) + r] = (int)(b & 0xFFFFu);
+      if (last) hints[(size_t)xcd * 2 * nrec + (ri ? nrec : 0) + hg.r] = (int)(b & 0xFFFFu);
       Drifts2<NAP>& D = s_dr[m][ri];
       if (keep) {
-        const RefGeo R = ri ? rg[1] : rg[0];
-        const long long pos16 = 16 * ((rs + qt - 1) >> 4) - rs;   // record position of the member's word grid
         const int d = (int)(b & 0xFFFFu) - DRIFT;
-        const long long pl = R.plo + 1 > 1 ? R.plo + 1 : 1;
-        const long long ph = R.rfn - k - IW < R.phi - IW - k ? R.rfn - k - IW : R.phi - IW - k;
-        const long long lo = pl + d - qt, hi = ph + d - qt;
-        D.U[slot] = (int)(R.rbase + pos16 - d);
-        D.lo[slot] = (int)(lo < -(1ll << 30) ? -(1ll << 30) : lo);
-        D.hi[slot] = (int)(hi > (1ll << 30) ? (1ll << 30) : hi);
+        D.U[slot] = hg.U0 - d;
+        D.lo[slot] = hg.pl + d;
+        D.hi[slot] = hg.ph + d;
         D.d[slot] = d;
       }
       if (ai == NAP - 1) D.n = slot + (keep ? 1 : 0);
@@ -1456,21 +1478,17 @@ k_cover_p(const uint32_t* __restrict__ p2, const uint8_t* __restrict__ e16, uint
   }
   cover_barrier();
   // ---- coverage: wave m = member m, lane l = windows 64 l .. 64 l + 63
-  const int m = __builtin_amdgcn_readfirstlane(t >> 6), l = t & 63;
-  long long rs = mrs[0], rn = mrn[0];
-#pragma unroll
-  for (int y = 1; y < QM; ++y) if (m == y) { rs = mrs[y]; rn = mrn[y]; }
-  const long long last = rn - k;
+  const int m = mw, l = lw;
+  const long long rs = me.rs, last = me.last;
+  const int lastrel = me.lastrel;
   uint32_t covS[4] = {0u, 0u, 0u, 0u};            // per segment: bit 2 i = window i covered
   bool mex = false;
   if ((dm0 >> m) & 1u) {
-    const long long p0 = rs + qt - 1, wb = (p0 >> 4) + 4 * l;
-    const int sh2 = 2 * (int)(p0 & 15);
+    const int sh2 = me.sh2;
     // (M: the lane's words wb .. wb + 6, eex: the exception bytes of the three
     // aligned dwords around them, both loaded at the start)
-    (void)PG_BOK(wb + LW <= (long long)n_p2 + 4 || wb > (long long)n_p2, 11, wb, n_p2);
-    (void)wb;
-    mex = eex != 0u;
+    (void)PG_BOK(me.wb + 4 * l + LW <= (long long)n_p2 + 4 || me.wb + 4 * l > (long long)n_p2, 11, me.wb + 4 * l, n_p2);
+    mex = (eex[0] | eex[1] | eex[2]) != 0u;
     const int L = k + 2;                           // context bases of a window
     const int P = L >= 16 ? 16 : L >= 8 ? 8 : L >= 4 ? 4 : 2;
     const uint32_t rsh = 2u * (uint32_t)(L - P);
@@ -1557,10 +1575,10 @@ k_cover_p(const uint32_t* __restrict__ p2, const uint8_t* __restrict__ e16, uint
   uint32_t nwk = 0, wmask = 0, cov[4];
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
-    const long long q0 = qt + 64 * l + 16 * s;
-    const bool interior = q0 > 0 && q0 + IW <= last;
+    const int rel = 64 * l + 16 * s;               // window q0 = qt + rel
+    const bool interior = (rel > 0 || qt > 0) && rel + IW <= lastrel;
     cov[s] = interior && !mex ? even_bits(covS[s]) : 0u;
-    const bool work = ((live >> m) & 1u) && q0 <= last && cov[s] != (1u << IW) - 1u;
+    const bool work = ((live >> m) & 1u) && rel <= lastrel && cov[s] != (1u << IW) - 1u;
     wmask |= (uint32_t)work << s;
     nwk += work ? 1u : 0u;
   }
@@ -1575,8 +1593,8 @@ k_cover_p(const uint32_t* __restrict__ p2, const uint8_t* __restrict__ e16, uint
 #pragma unroll
   for (int s = 0; s < 4; ++s)
     if ((wmask >> s) & 1u) {
-      if (PG_BOK(s_qbase + pos < qcap && rs >= 0 && qt + 64 * l + 16 * s <= rn, 15, s_qbase + pos, rs))
-        queue[sub * qcap + s_qbase + pos] = WorkItem{rs, rn - k, qt + 64 * l + 16 * s, cov[s], 0u};
+      if (PG_BOK(s_qbase + pos < qcap && rs >= 0 && qt + 64 * l + 16 * s <= last + k, 15, s_qbase + pos, rs))
+        queue[sub * qcap + s_qbase + pos] = WorkItem{rs, last, qt + 64 * l + 16 * s, cov[s], 0u};
       ++pos;
     }
 }
@@ -2469,10 +2487,18 @@ k_build_range(Recs I, TableView T, uint32_t rbits, uint32_t nparts, RdbgOut R, u
 // followers each, ord[1 + f] for f < nf[j], at stripe j - LEAD (the lead runs
 // LEAD stripes ahead).  Group g's members are descs[QM*g .. QM*g + QM); an
 // empty slot has r = -1 and the group's stripe.
+// The same thread writes its member's part of the group's GroupGeo (the
+// packed coverage pass's geometry: the struct's comment), and member 0's
+// thread the group's header: the two references' staged spans of the stripe,
+// [qt-1-DRIFT, qt+TILE+k+1+DRIFT) clipped to the record, as the words from rd0
+// (s_ref word RPADW), rbase = the s_ref base index of record position 0.
+// ref / ref2: the reference records (-1: none), [rfs, rfs + rfn) and
+// [r2s, r2s + r2n) in the compacted stream.
 constexpr uint32_t LEAD = 4;
 __global__ void k_tiles(const uint32_t* __restrict__ sched, uint32_t nj, uint32_t lead_stripes, uint32_t lead_off,
                         const long long* __restrict__ rec_start, const long long* __restrict__ rec_len,
-                        TileDesc* __restrict__ out, uint64_t ngroups) {
+                        TileDesc* __restrict__ out, GroupGeo* __restrict__ geo, uint64_t ngroups, int k, int ref,
+                        long long rfs, long long rfn, int ref2, long long r2s, long long r2n) {
   const uint32_t* off = sched;
   const uint32_t* nf = sched + nj + 1;
   const uint32_t* ord = nf + nj;
@@ -2486,18 +2512,61 @@ __global__ void k_tiles(const uint32_t* __restrict__ sched, uint32_t nj, uint32_
       if (off[mid] <= g) lo = mid; else hi = mid;
     }
     uint32_t i = (uint32_t)(g - off[lo]);
-    const bool lead = lo < lead_stripes;
-    int r = -1, stripe;
-    if (lead && i == 0) {
-      stripe = (int)lo;
-      if (m == 0) r = (int)ord[0];
-    } else {
-      if (lead) --i;
-      stripe = (int)(lo - lead_off);
-      const uint32_t f = i * QM + m;
-      if (f < nf[lo]) r = (int)ord[1 + f];
+    const bool lead = lo < lead_stripes, alone = lead && i == 0;   // alone: the lead's own tile
+    if (lead && !alone) --i;
+    const int stripe = alone ? (int)lo : (int)(lo - lead_off);
+    auto rec_of = [&](uint32_t mm) {                           // member mm's record, -1: an empty slot
+      if (alone) return mm == 0 ? (int)ord[0] : -1;
+      const uint32_t f = i * QM + mm;
+      return f < nf[lo] ? (int)ord[1 + f] : -1;
+    };
+    const int r = rec_of(m);
+    const long long rs = r >= 0 ? rec_start[r] : 0, rn = r >= 0 ? rec_len[r] : 0;
+    out[t] = TileDesc{rs, rn, r, stripe, 0};
+    const long long qt = (long long)stripe * TILE;
+    GroupGeo& G = geo[g];
+    MemberGeo mg;
+    mg.rs = rs;
+    mg.last = rn - k;
+    mg.wb = (rs + qt - 1) >> 4;
+    mg.r = r;
+    mg.sh2 = 2 * (int)((rs + qt - 1) & 15);
+    mg.lastrel = clamp30(rn - k - qt);
+    mg.arel = clamp30(rn - qt - 8 - ALEN);
+    const long long pos16 = 16 * mg.wb - rs;                   // record position of the member's word grid
+#pragma unroll
+    for (int ri = 0; ri < 2; ++ri) {
+      const long long s = ri ? r2s : rfs, n = ri ? r2n : rfn;
+      const long long plo = qt - 1 - DRIFT > 0 ? qt - 1 - DRIFT : 0;
+      const long long phi = qt + TILE + k + 1 + DRIFT < n ? qt + TILE + k + 1 + DRIFT : n;
+      const long long rd0 = (s + plo) >> 4, rbase = 16 * RPADW + s - 16 * rd0;
+      mg.U0[ri] = clamp30(rbase + pos16);
+      if (m == 0) {
+        RefSpan R;
+        R.rd0 = rd0;
+        R.rnw = clamp30(((s + phi + 15) >> 4) - rd0);
+        R.ph = clamp30((n < phi ? n : phi) - k - IW - qt);
+        R.ibhi0 = clamp30(rbase + qt + 8 + DRIFT);
+        R.lomin = clamp30(rbase + plo);
+        R.himax = clamp30(rbase + phi) - ALEN;
+        R.pl = clamp30((plo + 1 > 1 ? plo + 1 : 1) - qt);
+        G.ref[ri] = R;
+      }
     }
-    out[t] = r >= 0 ? TileDesc{rec_start[r], rec_len[r], r, stripe, 0} : TileDesc{0, 0, -1, stripe, 0};
+    G.mem[m] = mg;
+    if (m == 0) {
+      uint32_t bits = 0;
+#pragma unroll
+      for (uint32_t mm = 0; mm < QM; ++mm) {
+        const int rr = rec_of(mm);
+        const bool d0 = rr >= 0 && ref >= 0 && ref != rr;
+        bits |= (uint32_t)(rr >= 0) << mm | (uint32_t)d0 << (8 + mm) |
+                (uint32_t)(d0 && ref2 >= 0 && ref2 != rr) << (16 + mm);
+      }
+      G.qt = qt;
+      G.bits = bits;
+      G.pad = 0;
+    }
   }
 }
 
@@ -2802,14 +2871,18 @@ static uint64_t make_tiles(Ctx& c, const std::vector<uint8_t>& flag, bool follow
   for (size_t i = 0; i < nt.size(); ++i) sched[2 * nj + 1 + (follow ? 1 : 0) + i] = (uint32_t)nt[i].second;
   if (total * QM >= (1ull << 32)) throw Error(-22, "make_tiles: too many tiles");
   c.tile_desc.reserve(sizeof(TileDesc) * (QM * total + 1));
+  c.tile_geo.reserve(sizeof(GroupGeo) * (total + 1));
   if (total) {
     c.tile_pin.reserve(4 * sched.size());
     c.tile_sched.reserve(4 * sched.size());
     std::memcpy(c.tile_pin.p, sched.data(), 4 * sched.size());
     PG_HIP(hipMemcpyAsync(c.tile_sched.p, c.tile_pin.p, 4 * sched.size(), hipMemcpyHostToDevice, st));
+    const int r1 = c.k3_ref, r2 = c.k3_ref2;
     hipLaunchKernelGGL(k_tiles, dim3(grid_for(QM * total, 256, 2048)), dim3(256), 0, st,
                        c.tile_sched.as<uint32_t>(), nj, (uint32_t)lead_s, lead_off, c.rec_start.as<long long>(),
-                       c.rec_len.as<long long>(), c.tile_desc.as<TileDesc>(), total);
+                       c.rec_len.as<long long>(), c.tile_desc.as<TileDesc>(), c.tile_geo.as<GroupGeo>(), total, c.k,
+                       r1, (long long)(r1 >= 0 ? c.h_rec_start[r1] : 0), (long long)(r1 >= 0 ? c.h_rec_len[r1] : 0), r2,
+                       (long long)(r2 >= 0 ? c.h_rec_start[r2] : 0), (long long)(r2 >= 0 ? c.h_rec_len[r2] : 0));
     PG_HIP(hipGetLastError());
   }
   if (follow) {
@@ -3178,7 +3251,9 @@ static void enqueue_stageA(Ctx& c, uint64_t cap, uint64_t ntiles, int rc0, int e
 #ifdef PG_DEBUG_BOUNDS
   ensure_cls(c);                                            // (k_cover_p's debug check reads class bytes)
 #endif
+#if defined(PG_COVER_LEGACY) || defined(PG_DEBUG_BOUNDS)
   const uint8_t* cls = c.cls.as<uint8_t>();
+#endif
   const PackedCls pc = packed_cls(c);
   const dim3 b(IBLOCK);
   int nch = ntiles >= (uint64_t)K3_CHUNKS * K3_CHUNK_MIN ? K3_CHUNKS : 1;
@@ -3194,11 +3269,14 @@ static void enqueue_stageA(Ctx& c, uint64_t cap, uint64_t ntiles, int rc0, int e
   for (int i = 1; i <= nch; ++i) cb[i] = cb[i - 1] + (i == nch ? tailw : i == 1 ? headw : 16u);
   const uint32_t cbt = nch ? cb[nch] : 1u;
   uint64_t gc[8] = {}, qoff[8] = {}, qcapc[8] = {}, items = 0;
+  XcdBounds xb[8] = {};                                 // per chunk: every XCD's groups (make_tiles: fewer than 2^32)
   for (int i = 0; i < nch; ++i) {
     for (int x = 0; x < 8; ++x) {
       uint64_t t, te;
       xcd_chunk(ntiles, cb[i], cb[i + 1], cbt, (uint64_t)x, t, te);
       gc[i] = std::max<uint64_t>(gc[i], 8 * (te - t));
+      xb[i].g0[x] = (uint32_t)t;
+      xb[i].ge[x] = (uint32_t)te;
     }
     qcapc[i] = (gc[i] + NQ - 1) / NQ * (QM * CBLOCK);   // per sub-queue: a block queues <= QM * CBLOCK
     qoff[i] = items;
@@ -3238,10 +3316,15 @@ static void enqueue_stageA(Ctx& c, uint64_t cap, uint64_t ntiles, int rc0, int e
   const unsigned wgrid_last = c.k3_wblk >> 4 ? (unsigned)c.n_cu * (c.k3_wblk >> 4) : wgrid;
   auto* q = c.k3_queue.as<WorkItem>();
   auto* qn = reinterpret_cast<unsigned long long*>(c.k3_queue.as<uint8_t>() + qbytes);
-  const long long rfs = c.k3_ref >= 0 ? c.h_rec_start[c.k3_ref] : 0, rfn = c.k3_ref >= 0 ? c.h_rec_len[c.k3_ref] : 0;
+#if defined(PG_COVER_LEGACY) || defined(PG_DEBUG_BOUNDS)
+  const long long rfs = c.k3_ref >= 0 ? c.h_rec_start[c.k3_ref] : 0;
   const long long r2s = c.k3_ref2 >= 0 ? c.h_rec_start[c.k3_ref2] : 0;
+#endif
+#ifdef PG_COVER_LEGACY
+  const long long rfn = c.k3_ref >= 0 ? c.h_rec_len[c.k3_ref] : 0;
   const long long r2n = c.k3_ref2 >= 0 ? c.h_rec_len[c.k3_ref2] : 0;
   const TileDesc* td = c.tile_desc.as<TileDesc>();
+#endif
   bool short_done = false;
   if (!side) {
     PG_HIP(hipEventRecord(c.ev[0], s0));                       // s1 starts after the fills
@@ -3263,9 +3346,12 @@ static void enqueue_stageA(Ctx& c, uint64_t cap, uint64_t ntiles, int rc0, int e
 #endif
     if (gc[i])
       launch_cover_p(c.k3_anchors ? c.k3_anchors : NAP_DEFAULT, dim3((unsigned)gc[i]), s0, c.p2.as<uint32_t>(),
-                     c.e16.as<uint8_t>(), (uint64_t)(c.p2.cap / 4), cls, td, qi, qni, (unsigned long long)qcapc[i], c.k,
-                     c.k3_ref, rfs, rfn, c.k3_ref2, r2s, r2n, c.k3_hint.as<int>(), (int)c.n_records, ntiles,
-                     cb[i], cb[i + 1], cbt);
+                     c.e16.as<uint8_t>(), (uint64_t)(c.p2.cap / 4),
+#ifdef PG_DEBUG_BOUNDS
+                     cls, (long long)rfs, (long long)r2s,
+#endif
+                     c.tile_geo.as<GroupGeo>(), qi, qni, (unsigned long long)qcapc[i], c.k, c.k3_hint.as<int>(),
+                     (int)c.n_records, xb[i]);
     PG_HIP(hipGetLastError());
 #ifdef PG_DEBUG_BOUNDS
     for (int j = 0; j < nch; ++j)                 // this chunk's counters in range, the later ones still zero

@@ -271,6 +271,7 @@ struct Ctx {
   uint64_t build_gen = 0;         // bumped by every table build / merge
   DevBuf k3_hint;                 // int32 [8 XCDs][2 references][R]: last drift k_cover found
   DevBuf tile_desc;               // tile descriptors (record start / length / index / stripe)
+  DevBuf tile_geo;                // one GroupGeo per coverage group: the packed coverage pass's geometry (k_tiles)
   DevBuf k3_queue;                // segments left with work after the coverage pass, + counters
   std::vector<int64_t> tile_sig_len;   // record lengths / flags the tile list was built for
   std::vector<uint8_t> tile_sig_flag;

@@ -8,7 +8,8 @@ Each --tune argument is one variant (a comma-separated list of pg_tune
 settings by PG_TUNE_* name, or "base" for none).  Prints per variant the
 median, smallest and largest step, stage A / split / range spans (HIP
 events), stage A records, and whether every step's counts match the oracle
-digest of c3a; with --json, every step's wall time per variant as one JSON line."""
+digest of c3a; with --json, every step's wall time, range and stage A spans and (per batch) stage A
+records per variant as one JSON line."""
 import argparse
 import json
 import os
@@ -81,7 +82,7 @@ def main():
             ms = 1e3 * (time.perf_counter() - t1)
             ok = dig is None or (st.n_dbg, st.n_rdbg) == (dig["n_dbg"], dig["n_rdbg"])
             if step >= 2:
-                res[vi].append((ms, st.ms_parse, st.ms_insert, st.ms_split, st.ms_range, st.n_records_a, ok))
+                res[vi].append((ms, st.ms_parse, st.ms_insert, st.ms_split, st.ms_range, st.n_records_a, ok, b))
     for vi, v in enumerate(variants):
         a = np.array([r[:6] for r in res[vi]])
         med = np.median(a, axis=0)
@@ -90,7 +91,10 @@ def main():
                med[3], med[4], int(med[5]), all(r[6] for r in res[vi])), flush=True)
     if args.json:
         print(json.dumps({"ab_k3_steps_ms": {v: [round(r[0], 4) for r in res[vi]] for vi, v in enumerate(variants)},
-                          "range_ms": {v: [round(r[4], 4) for r in res[vi]] for vi, v in enumerate(variants)}}))
+                          "range_ms": {v: [round(r[4], 4) for r in res[vi]] for vi, v in enumerate(variants)},
+                          "stage_a_ms": {v: [round(r[2], 4) for r in res[vi]] for vi, v in enumerate(variants)},
+                          "n_records_a": {v: {str(b): [int(r[5]) for r in res[vi] if r[7] == b] for b in range(len(mms))}
+                                          for vi, v in enumerate(variants)}}))
 
 
 if __name__ == "__main__":
