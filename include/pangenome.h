@@ -530,6 +530,80 @@ int pg_freq_compare(pg_ctx* ctx, const uint64_t* bits, uint64_t n_labels, uint32
 int pg_freq_shared(pg_ctx* ctx, uint64_t* shared, uint64_t cap);              /* cap >= G * G      */
 int pg_freq_curve(pg_ctx* ctx, uint64_t* pan, uint64_t* core, uint64_t cap);  /* cap >= P * G each */
 
+/* ---- k-mer colours: the coloured de Bruijn graph - which genomes hold every
+ *      k-mer of the dBG.  Unlike the region labels it depends on no clustering
+ *      (-a, -w, -I): the exact k-mer spectrum (core, shell, unique), exact
+ *      k-mer distances between genomes and the k-mer pan / core growth curves
+ *      follow from it.  Integer only; OR is commutative, so the result depends
+ *      on the input alone, whatever the schedule.
+ * Input: a context with a parse and the dBG table of a build or load over
+ * that parse (whatever pg_dbg_export would return); rec_group [n_records]
+ * int32, the genome of each record in [0, n_groups) or -1 for "no genome";
+ * rec_flags [n_records] uint8 as pg_build_dbg takes it (NULL: all); rc0.
+ * Walked record: rec_flags[r] != 0 and rec_group[r] >= 0.  Its windows are
+ * exactly the ones pg_build_dbg inserts for that record under that rc0: the
+ * forward strand, and the reverse strand if rc0, the short-record rules for
+ * n <= k + 1 included.  The n < k sentinel window is left out: the table never
+ * holds it (pg_dbg_export appends the key 2^64 - 1 from a flag), so it is no
+ * key here either.  Only keys matter; the masks are not read.
+ * Keys and colours: K[0 .. n) = the table's plain keys in ascending order,
+ * exactly pg_dbg_export's without that sentinel; colour[i] = W =
+ * ceil(n_groups / 64) uint64 words, genome g being bit g % 64 of word g / 64
+ * as in pg_freq.  The bit is set iff some window of a walked record of genome
+ * g has the key K[i] - put differently, iff K[i] is in the dBG built from
+ * genome g's records alone.  A bit at or above n_groups is never set.
+ * Counts (each pointer may be NULL): *n_keys = n; *n_windows = the windows
+ * looked up; *n_missing = those whose key is not in the table - they colour
+ * nothing, which is no error and can only happen when the table was built
+ * from fewer records than are walked; *n_uncoloured = the keys with no bit.
+ * Spectrum: kmers_by_g[0 .. G] = the keys in exactly g genomes; index 0 equals
+ * *n_uncoloured.  Per genome: kmers = its keys; core = its keys found in all G
+ * genomes; unique = its keys found in it alone when G > 1 (with one genome
+ * everything is core, as in pg_freq); shell = the rest; core + shell + unique
+ * == kmers.
+ * Comparison (pg_kmer_compare): shared[g][h], pan[p][n] and core[p][n] exactly
+ * as pg_freq_compare defines them with "label" read as "key", over orders
+ * int32 [n_orders][G]; its result is its own: pg_freq, pg_freq_compare,
+ * pg_tree_nj and every region pass neither read nor drop it, nor it theirs.
+ * Lifetime: the colours stay on the device - 8 (W + 1) n bytes; twice that
+ * and 4 bytes per table slot while the call runs - until the next successful
+ * pg_kmer_colors, pg_kmer_colors_drop, or any call that replaces the dBG
+ * table (a parse, build, load or merge), after which the calls below return
+ * PG_EINVAL.  A successful pg_kmer_colors drops the previous comparison.
+ * PG_EINVAL, before any device work, the previous result kept: a NULL
+ * context; no parse or no table; rec_group == NULL; an entry outside
+ * [-1, n_groups); n_records different from the context's record count;
+ * n_groups == 0 with records.  n_groups > 32768 is PG_ERANGE, as in the
+ * comparison, and so is a table of 2^32 keys or more.  An allocation failure
+ * is PG_ENOMEM with the previous result kept. */
+int pg_kmer_colors(pg_ctx* ctx, const int32_t* rec_group, const uint8_t* rec_flags, uint64_t n_records,
+                   uint32_t n_groups, int rc0, uint64_t* n_keys, uint64_t* n_windows, uint64_t* n_missing,
+                   uint64_t* n_uncoloured);
+/* The keys and colours of the last pg_kmer_colors, bits [n][W] key-major;
+ * either pointer may be NULL (both: only *n is set, which may be NULL too);
+ * cap (keys) below n is PG_ERANGE. */
+int pg_kmer_colors_export(pg_ctx* ctx, uint64_t* keys, uint64_t* bits, uint64_t cap, uint64_t* n);
+/* kmers_by_g [G + 1] and the per-genome columns [G]; each may be NULL. */
+int pg_kmer_colors_spectrum(pg_ctx* ctx, uint64_t* kmers_by_g, uint64_t* g_kmers, uint64_t* g_core, uint64_t* g_shell,
+                            uint64_t* g_unique);
+/* The comparison of the colours where they lie; orders as pg_freq_compare
+ * takes them (PG_EINVAL for a row that is no permutation, or NULL with
+ * n_orders > 0; the previous comparison is kept).  Export: shared [G][G]
+ * (shared_cap >= G * G), pan and core [P][G] (curve_cap >= P * G each); each
+ * pointer may be NULL; a short cap is PG_ERANGE; PG_EINVAL before any
+ * pg_kmer_compare over the current colours. */
+int pg_kmer_compare(pg_ctx* ctx, const int32_t* orders, uint32_t n_orders);
+int pg_kmer_compare_export(pg_ctx* ctx, uint64_t* shared, uint64_t shared_cap, uint64_t* pan, uint64_t* core,
+                           uint64_t curve_cap);
+/* HIP events on the context's stream over the last pg_kmer_colors: ms_index =
+ * the key index before the colouring pass and the tables after it (rows
+ * brought into key order, spectrum), ms_colour = the colouring pass alone,
+ * ms_compare = the last pg_kmer_compare over these colours (0 before any);
+ * n_windows as pg_kmer_colors returned it. */
+int pg_kmer_colors_time(pg_ctx* ctx, double* ms_index, double* ms_colour, double* ms_compare, uint64_t* n_windows);
+/* Releases the colours and their comparison (no error when there are none). */
+int pg_kmer_colors_drop(pg_ctx* ctx);
+
 /* ---- genome tree: the third thing a pangenome study draws from the
  *      comparison - a tree of the genomes, by neighbour joining over a
  *      distance matrix.  Integer only (fixed point); the result depends on

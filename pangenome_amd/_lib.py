@@ -125,6 +125,13 @@ SIGNATURES = {
     "pg_freq_compare": (C.c_int, [_P, _P, C.c_uint64, C.c_uint32, _P, C.c_uint32]),
     "pg_freq_shared": (C.c_int, [_P, _P, C.c_uint64]),
     "pg_freq_curve": (C.c_int, [_P, _P, _P, C.c_uint64]),
+    "pg_kmer_colors": (C.c_int, [_P, _P, _P, C.c_uint64, C.c_uint32, C.c_int, _U64P, _U64P, _U64P, _U64P]),
+    "pg_kmer_colors_export": (C.c_int, [_P, _P, _P, C.c_uint64, _U64P]),
+    "pg_kmer_colors_spectrum": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "pg_kmer_compare": (C.c_int, [_P, _P, C.c_uint32]),
+    "pg_kmer_compare_export": (C.c_int, [_P, _P, C.c_uint64, _P, _P, C.c_uint64]),
+    "pg_kmer_colors_time": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), _U64P]),
+    "pg_kmer_colors_drop": (C.c_int, [_P]),
     "pg_tree_nj": (C.c_int, [_P, _P, C.c_uint32, _U64P]),
     "pg_tree_dist": (C.c_int, [_P, _P, C.c_uint64]),
     "pg_tree_joins": (C.c_int, [_P, _P, _P, _P, _P, C.c_uint64]),
@@ -854,6 +861,85 @@ class Context:
         pan, core = np.empty((P, G), np.uint64), np.empty((P, G), np.uint64)
         check(self.lib.pg_freq_curve(self.h, ptr(pan), ptr(core), P * G), "pg_freq_curve")
         return pan, core
+
+    # ---------------------------------------------------- k-mer colours
+    def kmer_colors(self, rec_group, n_groups: int, rec_flags=None, rc0: bool = True):
+        """The k-mer colours (pg_kmer_colors) of the dBG table in the context:
+        rec_group[r] = record r's genome in [0, n_groups) or -1; rec_flags as
+        build_dbg takes them (None: all); rc0 as the table was built.  Returns
+        (n_keys, n_windows, n_missing, n_uncoloured); the colours stay on the
+        device (kmer_colors_export / kmer_colors_spectrum / kmer_compare)
+        until kmer_colors_drop or a call that replaces the table."""
+        grp = np.ascontiguousarray(rec_group, dtype=np.int32).reshape(-1)
+        R = grp.shape[0]
+        if not R:
+            grp = np.full(1, -1, np.int32)               # (never NULL: an empty array's pointer may be)
+        f = None if rec_flags is None else np.ascontiguousarray(rec_flags, dtype=np.uint8)
+        if f is not None and not f.size:
+            f = None
+        out = [C.c_uint64() for _ in range(4)]
+        check(self.lib.pg_kmer_colors(self.h, ptr(grp), ptr(f), R, int(n_groups), int(bool(rc0)),
+                                      *[C.byref(x) for x in out]), "pg_kmer_colors")
+        self.kc_groups_n = int(n_groups)
+        return tuple(x.value for x in out)
+
+    def kmer_colors_export(self, keys: bool = True, bits: bool = True):
+        """(keys uint64 [n] ascending, bits uint64 [n, W]) of the last
+        kmer_colors() (pg_kmer_colors_export); a part not asked for is None."""
+        n = C.c_uint64()
+        check(self.lib.pg_kmer_colors_export(self.h, None, None, 0, C.byref(n)), "pg_kmer_colors_export")
+        W = (getattr(self, "kc_groups_n", 0) + 63) // 64
+        k = np.empty(n.value, np.uint64) if keys else None
+        b = np.empty((n.value, W), np.uint64) if bits else None
+        check(self.lib.pg_kmer_colors_export(self.h, ptr(k), ptr(b), n.value, C.byref(n)), "pg_kmer_colors_export")
+        return k, b
+
+    def kmer_colors_spectrum(self) -> dict:
+        """kmers_by_g [G + 1] and per genome g_kmers, g_core, g_shell,
+        g_unique [G] of the last kmer_colors() (pg_kmer_colors_spectrum)."""
+        G = getattr(self, "kc_groups_n", 0)
+        t = {"kmers_by_g": np.zeros(G + 1, np.uint64)}
+        for k in ("g_kmers", "g_core", "g_shell", "g_unique"):
+            t[k] = np.zeros(max(G, 1), np.uint64)
+        check(self.lib.pg_kmer_colors_spectrum(self.h, *[ptr(a) for a in t.values()]), "pg_kmer_colors_spectrum")
+        for k in ("g_kmers", "g_core", "g_shell", "g_unique"):
+            t[k] = t[k][:G]
+        return t
+
+    def kmer_compare(self, orders):
+        """The colours compared where they lie (pg_kmer_compare): orders int32
+        [P, G], every row a permutation (None: no order).  Returns (shared
+        [G, G], pan [P, G], core [P, G]) (pg_kmer_compare_export)."""
+        G = getattr(self, "kc_groups_n", 0)
+        o = np.zeros((0, G), np.int32) if orders is None else np.ascontiguousarray(orders, dtype=np.int32)
+        o = o.reshape(-1, G) if G else o.reshape(o.shape[0], 0)
+        P = o.shape[0]
+        if P and not o.size:
+            o = np.zeros(1, np.int32)                # (no genomes: P empty rows, but not NULL)
+        check(self.lib.pg_kmer_compare(self.h, ptr(o) if P else None, P), "pg_kmer_compare")
+        self.kc_orders_n = P
+        return self.kmer_compare_export()
+
+    def kmer_compare_export(self):
+        """(shared, pan, core) of the last kmer_compare() (pg_kmer_compare_export)."""
+        G, P = getattr(self, "kc_groups_n", 0), getattr(self, "kc_orders_n", 0)
+        s = np.zeros((G, G), np.uint64)
+        pan, core = np.zeros((P, G), np.uint64), np.zeros((P, G), np.uint64)
+        check(self.lib.pg_kmer_compare_export(self.h, ptr(s), G * G, ptr(pan), ptr(core), P * G),
+              "pg_kmer_compare_export")
+        return s, pan, core
+
+    def kmer_colors_time(self):
+        """(ms_index, ms_colour, ms_compare, n_windows) of the last kmer_colors()
+        (pg_kmer_colors_time)."""
+        a, b, d, n = C.c_double(), C.c_double(), C.c_double(), C.c_uint64()
+        check(self.lib.pg_kmer_colors_time(self.h, C.byref(a), C.byref(b), C.byref(d), C.byref(n)),
+              "pg_kmer_colors_time")
+        return a.value, b.value, d.value, n.value
+
+    def kmer_colors_drop(self):
+        """Release the colours and their comparison (pg_kmer_colors_drop)."""
+        check(self.lib.pg_kmer_colors_drop(self.h), "pg_kmer_colors_drop")
 
     # ---------------------------------------------------- genome tree
     def tree_nj(self, dist=None, n=None) -> int:

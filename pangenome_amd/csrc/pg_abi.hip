@@ -96,7 +96,7 @@ void pg_destroy(pg_ctx* x) {
                         &c.k3_hint, &c.part_cnt, &c.tile_cnt, &c.tile_off, &c.occ, &c.edge_tab, &c.pair_tab,
                         &c.edge_out, &c.edge_exp, &c.lab_tab, &c.lab_list, &c.rows_buf, &c.xyz_off,
                         &c.text_buf, &c.clu_text, &c.mk_mat, &c.fr_tab, &c.fr_spec, &c.fr_grp, &c.fr_text,
-                        &c.cmp_shared, &c.cmp_curve, &c.nj_dist, &c.rg_nodes, &c.rg_links, &c.rg_paths, &c.rg_steps, &c.rg_text,
+                        &c.cmp_shared, &c.cmp_curve, &c.kc_keys, &c.kc_bits, &c.kc_stat, &c.kc_shared, &c.kc_curve, &c.nj_dist, &c.rg_nodes, &c.rg_links, &c.rg_paths, &c.rg_steps, &c.rg_text,
                         &c.rs_tab, &c.rs_blob, &c.preload,
                         &c.dump_cnt};
   for (auto* b : bufs) b->release();
@@ -113,6 +113,7 @@ void pg_destroy(pg_ctx* x) {
   c.t_rs.destroy();
   c.t_nj.destroy();
   for (auto& t : c.t_bt) t.destroy();
+  for (auto& t : c.t_kc) t.destroy();
   for (auto& e : c.ev)
     if (e) (void)hipEventDestroy(e);
   for (auto e : c.cev)
@@ -912,6 +913,64 @@ int pg_freq_curve(pg_ctx* x, uint64_t* pan, uint64_t* core, uint64_t cap) {
     if (!x) throw pg::Error(PG_EINVAL, "pg_freq_curve: ctx is NULL");
     PG_HIP(hipSetDevice(x->c.device));
     pg::freq_curve(x->c, pan, core, cap);
+  });
+}
+
+int pg_kmer_colors(pg_ctx* x, const int32_t* rec_group, const uint8_t* rec_flags, uint64_t n_records, uint32_t n_groups,
+                   int rc0, uint64_t* n_keys, uint64_t* n_windows, uint64_t* n_missing, uint64_t* n_uncoloured) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_kmer_colors: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::kmer_colors(x->c, rec_group, rec_flags, n_records, n_groups, rc0, n_keys, n_windows, n_missing, n_uncoloured);
+  });
+}
+
+int pg_kmer_colors_export(pg_ctx* x, uint64_t* keys, uint64_t* bits, uint64_t cap, uint64_t* n) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_kmer_colors_export: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::kmer_colors_export(x->c, keys, bits, cap, n);
+  });
+}
+
+int pg_kmer_colors_spectrum(pg_ctx* x, uint64_t* kmers_by_g, uint64_t* g_kmers, uint64_t* g_core, uint64_t* g_shell,
+                            uint64_t* g_unique) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_kmer_colors_spectrum: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::kmer_colors_spectrum(x->c, kmers_by_g, g_kmers, g_core, g_shell, g_unique);
+  });
+}
+
+int pg_kmer_compare(pg_ctx* x, const int32_t* orders, uint32_t n_orders) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_kmer_compare: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::kmer_compare(x->c, orders, n_orders);
+  });
+}
+
+int pg_kmer_compare_export(pg_ctx* x, uint64_t* shared, uint64_t shared_cap, uint64_t* pan, uint64_t* core,
+                           uint64_t curve_cap) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_kmer_compare_export: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::kmer_compare_export(x->c, shared, shared_cap, pan, core, curve_cap);
+  });
+}
+
+int pg_kmer_colors_time(pg_ctx* x, double* ms_index, double* ms_colour, double* ms_compare, uint64_t* n_windows) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_kmer_colors_time: ctx is NULL");
+    pg::kmer_colors_time(x->c, ms_index, ms_colour, ms_compare, n_windows);
+  });
+}
+
+int pg_kmer_colors_drop(pg_ctx* x) {
+  return guard([&] {
+    if (!x) throw pg::Error(PG_EINVAL, "pg_kmer_colors_drop: ctx is NULL");
+    PG_HIP(hipSetDevice(x->c.device));
+    pg::kmer_colors_drop(x->c);
   });
 }
 

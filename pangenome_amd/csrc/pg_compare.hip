@@ -5,6 +5,9 @@
 //
 // Input: bits [n][W] (label-major: genome g is bit g % 64 of word g / 64 of a
 // label's row), on the device already (the last pg_freq's table) or uploaded.
+// compare_bits runs the steps over any such device table: pg_freq_compare and
+// pg_kmer_compare (pg_colors.hip, the "labels" being the dBG's keys) differ
+// only in where the bits come from and where the result goes.
 //
 // Steps, each its own launch on c.stream (no hand-shake inside a kernel):
 //   a. k_cmp_transpose  bits [n][W] -> T [G][NW], genome-major bit rows: bit
@@ -208,60 +211,42 @@ __global__ void __launch_bounds__(RG_BLOCK) k_cmp_curves(const ull* __restrict__
   }
 }
 
-void freq_compare(Ctx& c, const uint64_t* h_bits, uint64_t n, uint32_t G, const int32_t* orders, uint32_t P) {
-  // ---- arguments: everything refused here leaves the previous result in place
-  const uint32_t W = (uint32_t)(((uint64_t)G + 63) / 64);
-  if (!h_bits) {
-    if (!c.fr_ready) throw Error(-22, "pg_freq_compare: no frequency table (call pg_freq first, or pass bits)");
-    if (G != c.fr_groups)
-      throw Error(-22, "pg_freq_compare: " + std::to_string(G) + " genomes, the table has " +
-                           std::to_string(c.fr_groups));
-    n = c.fr_n;
-  }
-  if (G == 0 && n) throw Error(-22, "pg_freq_compare: n_groups is 0 with labels");
-  if (!orders && P) throw Error(-22, "pg_freq_compare: orders is NULL");
+// the arguments every comparison shares, checked before any device work
+void compare_check(const char* what, uint64_t n, uint32_t G, const int32_t* orders, uint32_t P) {
+  const std::string w(what);
+  if (G == 0 && n) throw Error(-22, w + ": n_groups is 0 with labels");
+  if (!orders && P) throw Error(-22, w + ": orders is NULL");
   if (G > CMP_MAX_GROUPS)
-    throw Error(-34, "pg_freq_compare: " + std::to_string(G) + " genomes: the matrix is dense, at most " +
+    throw Error(-34, w + ": " + std::to_string(G) + " genomes: the matrix is dense, at most " +
                          std::to_string(CMP_MAX_GROUPS));
-  {
-    std::vector<uint8_t> seen(G);
-    for (uint32_t p = 0; p < P; ++p) {
-      std::fill(seen.begin(), seen.end(), 0);
-      for (uint32_t i = 0; i < G; ++i) {
-        const int32_t g = orders[(uint64_t)p * G + i];
-        if (g < 0 || (uint32_t)g >= G || seen[g])
-          throw Error(-22, "pg_freq_compare: order " + std::to_string(p) + " is not a permutation of 0.." +
-                               std::to_string(G) + "-1 (entry " + std::to_string(i) + " = " + std::to_string(g) + ")");
-        seen[g] = 1;
-      }
+  std::vector<uint8_t> seen(G);
+  for (uint32_t p = 0; p < P; ++p) {
+    std::fill(seen.begin(), seen.end(), 0);
+    for (uint32_t i = 0; i < G; ++i) {
+      const int32_t g = orders[(uint64_t)p * G + i];
+      if (g < 0 || (uint32_t)g >= G || seen[g])
+        throw Error(-22, w + ": order " + std::to_string(p) + " is not a permutation of 0.." + std::to_string(G) +
+                             "-1 (entry " + std::to_string(i) + " = " + std::to_string(g) + ")");
+      seen[g] = 1;
     }
   }
-  if (h_bits && (G & 63)) {
-    const uint64_t above = ~0ull << (G & 63);
-    for (uint64_t l = 0; l < n; ++l)
-      if (h_bits[l * W + W - 1] & above)
-        throw Error(-22, "pg_freq_compare: row " + std::to_string(l) + " has a bit at or above genome " +
-                             std::to_string(G));
-  }
+}
 
-  // ---- buffers (an allocation failure leaves the previous result in place)
+// Steps a to c over a device bit table [n][W]: shared [G][G] and curve [2][P][G] (reserved and zeroed here)
+// hold the result when the stream has drained; the caller owns both and decides what they replace.
+void compare_bits(Ctx& c, const char* what, const ull* bits, uint64_t n, uint32_t G, const int32_t* orders,
+                  uint32_t P, DevBuf& shared, DevBuf& curve) {
+  compare_check(what, n, G, orders, P);
+  const uint32_t W = (uint32_t)(((uint64_t)G + 63) / 64);
+  // ---- buffers (an allocation failure leaves the caller's previous result in place)
   const uint64_t NW = ((n + 63) / 64 + 1) & ~1ull;
   const size_t sh_bytes = 8 * (size_t)G * G, cv_bytes = 8 * (size_t)P * G;
-  DevBuf up, tr, ord, shared, curve;
+  DevBuf tr, ord;
   shared.reserve(sh_bytes + 16);
   curve.reserve(2 * cv_bytes + 16);
   PG_HIP(hipMemsetAsync(shared.p, 0, sh_bytes + 16, c.stream));
   PG_HIP(hipMemsetAsync(curve.p, 0, 2 * cv_bytes + 16, c.stream));
   if (n && G) {
-    const ull* bits;
-    if (h_bits) {
-      up.reserve(8 * (size_t)W * n);
-      PG_HIP(hipMemcpyAsync(up.p, h_bits, 8 * (size_t)W * n, hipMemcpyHostToDevice, c.stream));
-      bits = up.as<ull>();
-    } else {
-      // the presence words inside c.fr_tab: after label, rows, plus, bases, min, max (pg_freq.hip)
-      bits = c.fr_tab.as<ull>() + 6 * n;
-    }
     tr.reserve(8 * (size_t)G * NW);
     ull* T = tr.as<ull>();
     const unsigned cus = (unsigned)std::max(1, c.n_cu);
@@ -302,7 +287,40 @@ void freq_compare(Ctx& c, const uint64_t* h_bits, uint64_t n, uint32_t G, const 
       }
     }
   }
-  c.sync();
+  c.sync();                                  // (tr and ord are read until here)
+}
+
+void freq_compare(Ctx& c, const uint64_t* h_bits, uint64_t n, uint32_t G, const int32_t* orders, uint32_t P) {
+  // ---- arguments: everything refused here leaves the previous result in place
+  const uint32_t W = (uint32_t)(((uint64_t)G + 63) / 64);
+  if (!h_bits) {
+    if (!c.fr_ready) throw Error(-22, "pg_freq_compare: no frequency table (call pg_freq first, or pass bits)");
+    if (G != c.fr_groups)
+      throw Error(-22, "pg_freq_compare: " + std::to_string(G) + " genomes, the table has " +
+                           std::to_string(c.fr_groups));
+    n = c.fr_n;
+  }
+  compare_check("pg_freq_compare", n, G, orders, P);
+  if (h_bits && (G & 63)) {
+    const uint64_t above = ~0ull << (G & 63);
+    for (uint64_t l = 0; l < n; ++l)
+      if (h_bits[l * W + W - 1] & above)
+        throw Error(-22, "pg_freq_compare: row " + std::to_string(l) + " has a bit at or above genome " +
+                             std::to_string(G));
+  }
+  DevBuf up, shared, curve;
+  const ull* bits = nullptr;
+  if (n && G) {
+    if (h_bits) {
+      up.reserve(8 * (size_t)W * n);
+      PG_HIP(hipMemcpyAsync(up.p, h_bits, 8 * (size_t)W * n, hipMemcpyHostToDevice, c.stream));
+      bits = up.as<ull>();
+    } else {
+      // the presence words inside c.fr_tab: after label, rows, plus, bases, min, max (pg_freq.hip)
+      bits = c.fr_tab.as<ull>() + 6 * n;
+    }
+  }
+  compare_bits(c, "pg_freq_compare", bits, n, G, orders, P, shared, curve);
   // ---- the new result replaces the previous one
   c.cmp_shared.swap(shared);
   c.cmp_curve.swap(curve);

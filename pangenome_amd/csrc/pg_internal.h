@@ -346,6 +346,19 @@ struct Ctx {
   uint64_t bt_cells = 0;          // R x the sum of m^2 over a tree's joins
   uint64_t bt_scratch = 0;        // pg_tune: device bytes of a batch of replicates (0 = default)
   int bt_form_tune = 0;           // pg_tune: 0 = by size, 1 = LDS where legal, 2 = global scratch, 3 = per-join launches
+  // ---- k-mer colours (pg_colors.hip): the result of the last pg_kmer_colors, valid while kc_gen == build_gen
+  // (no other pass reads or drops it)
+  DevBuf kc_keys;                 // uint64 [n]: the table's plain keys, ascending
+  DevBuf kc_bits;                 // uint64 [n][W]: the genomes of every key
+  DevBuf kc_stat;                 // uint64 [G + 1] keys by number of genomes, then [2][G]: non-core keys, unique keys per genome
+  uint64_t kc_n = 0, kc_gen = 0, kc_windows = 0, kc_missing = 0;
+  uint32_t kc_groups = 0, kc_words = 0;
+  bool kc_ready = false;
+  DevBuf kc_shared, kc_curve;     // the last pg_kmer_compare: uint64 [G][G], [2][P][G] (a successful pg_kmer_colors drops it)
+  uint32_t kc_cmp_orders = 0;
+  bool kc_cmp_ready = false;
+  Timer t_kc[4];                  // the index, the colouring pass, the tables after it, the comparison
+  double ms_kc_index = 0, ms_kc_colour = 0, ms_kc_compare = 0;
   // ---- region graph (pg_region.hip): the result of the last pg_region_graph
   DevBuf rg_nodes;                // [n] label, rows, max length; uint32 [n] links out, links in
   DevBuf rg_links;                // [n] from, to, count; uint32 [n] genomes
@@ -576,6 +589,26 @@ void freq_compare(Ctx& c, const uint64_t* h_bits, uint64_t n_labels, uint32_t n_
                   uint32_t n_orders);
 void freq_shared(Ctx& c, uint64_t* shared, uint64_t cap);
 void freq_curve(Ctx& c, uint64_t* pan, uint64_t* core, uint64_t cap);
+
+// the comparison of any device bit table bits [n][W] (pg_freq_compare's and pg_kmer_compare's work): the orders
+// checked (-22 in `what`'s name), then shared [G][G] and curve [2][P][G] filled; nothing of the context is replaced
+void compare_bits(Ctx& c, const char* what, const unsigned long long* d_bits, uint64_t n, uint32_t G,
+                  const int32_t* orders, uint32_t P, DevBuf& shared, DevBuf& curve);
+void compare_check(const char* what, uint64_t n, uint32_t G, const int32_t* orders, uint32_t P);
+
+// pg_colors.hip
+// The k-mer colours: which genomes hold every key of the dBG table (include/pangenome.h, "k-mer colours");
+// replaces the context's previous colours only when it succeeds.
+void kmer_colors(Ctx& c, const int32_t* rec_group, const uint8_t* rec_flags, uint64_t n_records, uint32_t n_groups,
+                 int rc0, uint64_t* n_keys, uint64_t* n_windows, uint64_t* n_missing, uint64_t* n_uncoloured);
+void kmer_colors_export(Ctx& c, uint64_t* keys, uint64_t* bits, uint64_t cap, uint64_t* n);
+void kmer_colors_spectrum(Ctx& c, uint64_t* kmers_by_g, uint64_t* g_kmers, uint64_t* g_core, uint64_t* g_shell,
+                          uint64_t* g_unique);
+void kmer_compare(Ctx& c, const int32_t* orders, uint32_t n_orders);
+void kmer_compare_export(Ctx& c, uint64_t* shared, uint64_t shared_cap, uint64_t* pan, uint64_t* core,
+                         uint64_t curve_cap);
+void kmer_colors_time(Ctx& c, double* ms_index, double* ms_colour, double* ms_compare, uint64_t* n_windows);
+void kmer_colors_drop(Ctx& c);
 
 // pg_tree.hip
 // The neighbour-joining tree of a distance matrix (h_dist NULL: formed from the

@@ -1540,10 +1540,11 @@ def entry_point(argv, out=None, shard_factory=None, device=None, dev_index: int 
     # variable sites), whose alleles need the ranks' per-(allele, genome) records, and -b (the sites between anchors),
     # whose anchors need every rank's genomes of a label, and -V (their alleles as sequences), which reads them, and
     # -A (the alleles' alignments), which reads -V's, and -L (their band form), which needs -A, and -T (the genome
-    # tree), which reads one process's comparison, and -B (its support), which needs -T
+    # tree), which reads one process's comparison, and -B (its support), which needs -T, and -K (the k-mer colours), which
+    # walks every genome's records against one table
     bad = (not qry or n_orders is None or args["-l"] != "0" or args["-s"] != "0" or args["-v"] != "0" or
            args["-b"] != "0" or args["-V"] != "" or args["-A"] != "0" or args["-L"] != "0" or
-           args["-T"] != "0" or args["-B"] != "0")
+           args["-T"] != "0" or args["-B"] != "0" or args["-K"] != "0")
     clu = None if bad else cluster_args(args)
     if clu is None:
         if dist.get_rank() == 0:

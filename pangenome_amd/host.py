@@ -1041,12 +1041,13 @@ def freq_compare(bits, n_groups: int, orders):
     return shared, pan, core
 
 
-def write_compare_files(prefix: str, names, shared, orders, pan, core) -> None:
+def write_compare_files(prefix: str, names, shared, orders, pan, core, tag: str = "_fr_", curve: bool = True) -> None:
     """The four `-p` files of `prefix` (the input's path): `_fr_shared.tsv`
     (the matrix), `_fr_jaccard.tsv` (1 - shared / union, six decimals; 0 for an
     empty union), `_fr_curve.tsv` (per number of genomes the sum, minimum and
     maximum of pan and core over the orders) and `_fr_compare.npz`; each is
-    written to `.tmp` and renamed when whole."""
+    written to `.tmp` and renamed when whole.  tag: what stands for `_fr_` in
+    the names (`_km_`: the k-mer colours' files); curve False: no curve file."""
     s = np.asarray(shared, _U64)
     G = s.shape[0]
     o = np.asarray(orders, np.int32).reshape(-1, G) if G else np.zeros((len(orders), 0), np.int32)
@@ -1060,23 +1061,92 @@ def write_compare_files(prefix: str, names, shared, orders, pan, core) -> None:
         os.replace(fn + ".tmp", fn)
     head = b"#genome" + b"".join(b"\t" + x for x in nm) + b"\n"
     sl = s.tolist()
-    whole("_fr_shared.tsv", lambda f: f.write(head + b"".join(
+    whole(tag + "shared.tsv", lambda f: f.write(head + b"".join(
         nm[g] + "".join("\t%d" % v for v in sl[g]).encode() + b"\n" for g in range(G))))
 
     def jac(g, h):
         u = sl[g][g] + sl[h][h] - sl[g][h]
         return "\t%.6f" % (1.0 - sl[g][h] / u if u else 0.0)
-    whole("_fr_jaccard.tsv", lambda f: f.write(head + b"".join(
+    whole(tag + "jaccard.tsv", lambda f: f.write(head + b"".join(
         nm[g] + "".join(jac(g, h) for h in range(G)).encode() + b"\n" for g in range(G))))
     P = o.shape[0]
     cols = [[[int(x) for x in a[:, i].tolist()] for i in range(G)] for a in (pan, core)]
     stat = lambda v: (sum(v), min(v) if v else 0, max(v) if v else 0)
-    whole("_fr_curve.tsv", lambda f: f.write((
+    curve and whole(tag + "curve.tsv", lambda f: f.write((
         "#genomes\torders\tpan_sum\tpan_min\tpan_max\tcore_sum\tcore_min\tcore_max\n" + "".join(
             "%d\t%d\t%d\t%d\t%d\t%d\t%d\t%d\n" % ((i + 1, P) + stat(cols[0][i]) + stat(cols[1][i]))
             for i in range(G))).encode()))
     gn = np.array(nm, dtype=np.bytes_) if nm else np.zeros(0, "S1")
-    whole("_fr_compare.npz", lambda f: np.savez(f, genomes=gn, shared=s, orders=o, pan=pan, core=core))
+    whole(tag + "compare.npz", lambda f: np.savez(f, genomes=gn, shared=s, orders=o, pan=pan, core=core))
+
+
+# -------------------------------------------------------------- k-mer colours
+def kmer_colors(key_sets, n_groups: int, keys=None) -> dict:
+    """The k-mer colours' specification (pg_kmer_colors computes the same on
+    the device; include/pangenome.h, "k-mer colours", has the definition).
+    key_sets: per genome 0 .. n_groups - 1 a sorted uint64 key array, the keys
+    of the dBG of that genome's records alone; keys: the table's keys (None:
+    the union of the sets; a key of no set is uncoloured; a set's key that the
+    table lacks colours nothing).  Returns keys (ascending), bits (uint64
+    [n, ceil(n_groups / 64)], genome g = bit g % 64 of word g / 64),
+    n_genomes, kmers_by_g [n_groups + 1], g_kmers, g_core, g_shell, g_unique
+    (unique only when n_groups > 1) and shared (freq_compare's, over the keys)."""
+    G = int(n_groups)
+    if len(key_sets) != G:
+        raise ValueError("kmer_colors: %d key sets for %d genomes" % (len(key_sets), G))
+    W = (G + 63) // 64
+    sets = [np.unique(np.asarray(k, dtype=_U64).reshape(-1)) for k in key_sets]
+    if keys is None:
+        keys = np.unique(np.concatenate(sets)) if sets else np.zeros(0, _U64)
+    else:
+        keys = np.unique(np.asarray(keys, dtype=_U64).reshape(-1))
+    n = keys.shape[0]
+    bits = np.zeros((n, W), _U64)
+    for g, ks in enumerate(sets):
+        i = np.searchsorted(keys, ks)
+        i = i[(i < n) & (keys[np.minimum(i, max(n - 1, 0))] == ks)] if n else i[:0]
+        bits[i, g >> 6] |= _U64(1) << _U64(g & 63)
+    ng = _popcount_rows(bits)
+    t = {"n_groups": G, "keys": keys, "bits": bits, "n_genomes": ng,
+         "kmers_by_g": np.bincount(ng, minlength=G + 1).astype(_U64)}
+    core, uniq = ng == G, (ng == 1) & (G > 1)
+    for name, sel in (("g_kmers", slice(None)), ("g_core", core), ("g_unique", uniq)):
+        b = bits[sel]
+        t[name] = np.array([int(((b[:, g >> 6] >> _U64(g & 63)) & _U64(1)).sum()) for g in range(G)], dtype=_U64)
+    t["g_shell"] = t["g_kmers"] - t["g_core"] - t["g_unique"]
+    t["shared"] = freq_compare(bits, G, None)[0]
+    return t
+
+
+def kmer_distance(shared) -> np.ndarray:
+    """d[g][h] = shared[g][g] + shared[h][h] - 2 shared[g][h]: the keys in
+    exactly one of the two genomes, as pg_tree_nj takes a host matrix;
+    ValueError, naming the limit, for an entry above pg_tree_nj's 2^31."""
+    s = np.asarray(shared, _U64)
+    dg = s.diagonal()
+    d = dg[:, None] + dg[None, :] - _U64(2) * s
+    if d.size and int(d.max()) > TREE_MAX_DIST:
+        raise ValueError("-K with -T: a k-mer distance of %d is above pg_tree_nj's limit of 2^31 = %d"
+                         % (int(d.max()), TREE_MAX_DIST))
+    return d
+
+
+def write_kmer_files(prefix: str, table: dict, genome_names) -> None:
+    """The first two `-K` files of `prefix` (the input's path): `_km_spectrum.tsv`
+    (`#genomes kmers`, one line for each of 0 .. G) and `_km_genomes.tsv`
+    (`#genome kmers core shell unique`) from kmers_by_g and the g_ columns of
+    table; each is written to `.tmp` and renamed when whole."""
+    def whole(suffix, fill):
+        fn = prefix + suffix
+        with open(fn + ".tmp", "wb") as f:
+            fill(f)
+        os.replace(fn + ".tmp", fn)
+    by_g = [int(x) for x in table["kmers_by_g"]]
+    whole("_km_spectrum.tsv", lambda f: f.write(("#genomes\tkmers\n" + "".join(
+        "%d\t%d\n" % (g, v) for g, v in enumerate(by_g))).encode()))
+    cols = [[int(x) for x in table[k]] for k in ("g_kmers", "g_core", "g_shell", "g_unique")]
+    whole("_km_genomes.tsv", lambda f: f.write(b"#genome\tkmers\tcore\tshell\tunique\n" + b"".join(
+        bytes(nm) + ("\t%d\t%d\t%d\t%d\n" % x).encode() for nm, x in zip(genome_names, zip(*cols)))))
 
 
 # ---------------------------------------------------------------- genome tree
@@ -1204,14 +1274,15 @@ def tree_newick(names, joins, root, support=None) -> bytes:
     return b"".join(out)
 
 
-def write_tree_files(prefix: str, names, dist, joins, root, var: bool = False) -> None:
+def write_tree_files(prefix: str, names, dist, joins, root, var: bool = False, tag: str = "_fr_") -> None:
     """The `-T` files of `prefix` (the input's path): `_fr_dist.tsv` (the
     distance matrix in `_fr_shared.tsv`'s layout), `_fr_tree.nwk`,
     `_fr_tree.tsv` (per join the node it makes, its two children and their
     lengths as the Newick prints them, then one `#root` line: the children,
     then their lengths) and `_fr_tree.npz`; var: the tree of the differences,
     `_fr_vardist.tsv` and `_fr_vartree.nwk` alone.  Each is written to `.tmp`
-    and renamed when whole."""
+    and renamed when whole.  tag: what stands for `_fr_` in the names (`_km_`:
+    the k-mer tree's files)."""
     d = np.asarray(dist, _U64)
     n = d.shape[0]
     nm = [bytes(x) for x in names]
@@ -1223,20 +1294,20 @@ def write_tree_files(prefix: str, names, dist, joins, root, var: bool = False) -
         os.replace(fn + ".tmp", fn)
     head = b"#genome" + b"".join(b"\t" + x for x in nm) + b"\n"
     dl = d.tolist()
-    whole("_fr_vardist.tsv" if var else "_fr_dist.tsv", lambda f: f.write(head + b"".join(
+    whole(tag + ("vardist.tsv" if var else "dist.tsv"), lambda f: f.write(head + b"".join(
         nm[g] + "".join("\t%d" % v for v in dl[g]).encode() + b"\n" for g in range(n))))
-    whole("_fr_vartree.nwk" if var else "_fr_tree.nwk", lambda f: f.write(tree_newick(nm, joins, root)))
+    whole(tag + ("vartree.nwk" if var else "tree.nwk"), lambda f: f.write(tree_newick(nm, joins, root)))
     if var:
         return
     cols = [[int(x) for x in joins[k]] for k in ("left", "right", "left_len", "right_len")]
     child, ln = [int(x) for x in root[0]], [int(x) for x in root[1]]
-    whole("_fr_tree.tsv", lambda f: f.write(
+    whole(tag + "tree.tsv", lambda f: f.write(
         b"#node\tleft\tright\tleft_len\tright_len\n" + b"".join(
             b"%d\t%d\t%d\t%s\t%s\n" % (n + t, a, b, tree_len_text(x), tree_len_text(y))
             for t, (a, b, x, y) in enumerate(zip(*cols))) +
         b"#root" + b"".join(b"\t%d" % c for c in child) + b"".join(b"\t" + tree_len_text(v) for v in ln) + b"\n"))
     gn = np.array(nm, dtype=np.bytes_) if nm else np.zeros(0, "S1")
-    whole("_fr_tree.npz", lambda f: np.savez(
+    whole(tag + "tree.npz", lambda f: np.savez(
         f, genomes=gn, dist=d, left=np.asarray(joins["left"], np.uint32), right=np.asarray(joins["right"], np.uint32),
         left_len=np.asarray(joins["left_len"], _U64), right_len=np.asarray(joins["right_len"], _U64),
         root_child=np.asarray(root[0], np.uint32), root_len=np.asarray(root[1], _U64),

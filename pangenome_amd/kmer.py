@@ -9,7 +9,7 @@ runs in libpangenome_hip.so on an MI355X (pangenome_amd/csrc).  Mirrors:
   dbg2rdbg     :1313-1321                rdBG (K5 degree scan + compaction)
   seq2graph    :1853-1951                edges -> .xyz -> mcl -> labels -> rows
   dump / load_on_disk  :243-335         `<in>_db.npz` (oakht slot layout)
-  entry_point  :1971-2146                CLI (-i -k -n -c -r -d -R -D; ours: -a -w -g -p -l -s -v -b -V -A -L -T)
+  entry_point  :1971-2146                CLI (-i -k -n -c -r -d -R -D; ours: -a -w -g -p -l -s -v -b -V -A -L -T -B -K)
 
 Usage:  python -m pangenome_amd -i genomes.fa -k 27 > result.tab
 """
@@ -134,6 +134,7 @@ class DeviceGraph:
         self.rec_ptr = rec["ptr"]
         self.shape = host.FileShape.from_bytes(self.buf, self.hdr_start, self.hdr_len)
         self.reduced = False
+        self.dbg_flags = None                    # the record flags of the dBG pass (seq2rdbg; -K walks the same records)
 
     @property
     def size(self):
@@ -174,6 +175,7 @@ def seq2rdbg(qry, kmer=13, bits=5, Ns=1e6, chunk=2 ** 32, brkpt="./breakpoint", 
         flags, extra = host.plan_dbg(g.seq_len, g.shape, bool(rc), int(Ns), int(chunk))
         if extra or not flags.all():                      # (cannot happen: bases <= bytes)
             g.stats = g.ctx.build_dbg(flags, extra, bool(rc))
+        g.dbg_flags = flags
         return g
     g = DeviceGraph(qry, kmer, device, ctx=ctx)
     if on_parsed is not None:
@@ -194,6 +196,7 @@ def seq2rdbg(qry, kmer=13, bits=5, Ns=1e6, chunk=2 ** 32, brkpt="./breakpoint", 
         host.write_db_npz_from(qry + "_db_brkpt", cap, size, lambda fd, offs: g.ctx.dbg_dump_fd(fd, offs, cap),
                                offset=int(g.rec_ptr[last]))
     g.stats = g.ctx.build_dbg(flags, extra, bool(rc))
+    g.dbg_flags = flags
     return g
 
 
@@ -258,7 +261,7 @@ def rdbg_edges(g: DeviceGraph, Ns, chunk, rc, brkpt="", keep_on_device=False):
 def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_dict=None, saved=None,
               hashfunc=None, jit=True, chunk=2 ** 33, rc=False, cluster=True, out=None, min_weight=1, groups=None,
               orders=0, links=False, seqs=False, inflation2=3, sites=False, bubbles=0, variants="", align=False,
-              align_band=False, tree=False, boot=0):
+              align_band=False, tree=False, boot=0, kmers=False, rc0=True):
     """:1853-1951: edge weights -> `<qry>_rdbg_weight.xyz` -> mcl (or reuse)
     -> label dictionary -> print the region rows.  The edges, the label
     table, the rows and both texts are made on the device; the host writes
@@ -309,7 +312,11 @@ def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_
     with tree): that many bootstrap replicates rate every join of each tree
     (pg_tree_bootstrap) right after its files, as `<qry>_fr_tree_support.nwk`,
     `_fr_tree_support.tsv` and `_fr_tree_boot.npz`, and for the second tree
-    `_fr_vartree_support.nwk` and `_fr_vartree_support.tsv`."""
+    `_fr_vartree_support.nwk` and `_fr_vartree_support.tsv`.  kmers (-K, with
+    groups; rc0: the dBG's strands): last of all the dBG still in the context
+    is coloured (pg_kmer_colors: the genomes of every k-mer, over the records
+    the dBG pass inserted) and the `<qry>_km_*` files written (write_kmers);
+    nothing is printed and no other file changes."""
     out = out or sys.stdout
     g = rdbg_dict
     res = rdbg_edges(g, Ns, chunk, rc, brkpt=brkpt, keep_on_device=True)
@@ -396,6 +403,8 @@ def seq2graph(qry, kmer=13, bits=5, Ns=1e6, brkpt="./breakpoint_rdbg.npz", rdbg_
                     write_align(g, qry, names, flags, groups, variants, bool(align_band))
                     if tree:
                         write_var_tree(g, qry, gnames, boot=int(boot))
+        if kmers:
+            write_kmers(g, qry, names, flags, groups, bool(rc0), int(orders), bool(tree))
     gen = g.ctx.label_gen
     return LabelTable(loader=lambda: g.ctx.labels(gen))           # (raises once a later label pass replaced it)
 
@@ -495,6 +504,33 @@ def write_var_tree(g, qry, gnames, boot=0):
     host.write_tree_files(qry, gnames, g.ctx.tree_dist(), joins, root, var=True)
     if boot:
         write_tree_support(g, qry, gnames, joins, root, boot, bits=bits)
+
+
+def write_kmers(g, qry, names, flags, groups, rc0, n_orders, tree):
+    """-K: the dBG in the context coloured by write_freq's genomes
+    (pg_kmer_colors) over the records the dBG pass inserted (g.dbg_flags)
+    that have a genome - the ones the row pass walks, flags - as
+    `<qry>_km_spectrum.tsv` and `_km_genomes.tsv`; the colours compared where they lie (pg_kmer_compare,
+    write_compare's orders) as `_km_shared.tsv`, `_km_jaccard.tsv`,
+    `_km_compare.npz` and, with n_orders, `_km_curve.tsv`; tree: the
+    neighbour-joining tree of d = the k-mers in exactly one of two genomes
+    (formed here from the shared matrix; this replaces the context's tree,
+    whose files are written by now) as `_km_dist.tsv`, `_km_tree.nwk`,
+    `_km_tree.tsv` and `_km_tree.npz`.  The colours are dropped afterwards."""
+    dflags = g.dbg_flags if g.dbg_flags is not None else np.ones(len(names), np.uint8)
+    rec_group, gnames = host.assign_groups(names, flags, groups)
+    G = len(gnames)
+    try:
+        g.ctx.kmer_colors(rec_group, G, rec_flags=dflags, rc0=rc0)
+        host.write_kmer_files(qry, g.ctx.kmer_colors_spectrum(), gnames)
+        orders = host.compare_orders(G, n_orders)
+        shared, pan, core = g.ctx.kmer_compare(orders)
+        host.write_compare_files(qry, gnames, shared, orders, pan, core, tag="_km_", curve=bool(n_orders))
+    finally:
+        g.ctx.kmer_colors_drop()
+    if tree:
+        g.ctx.tree_nj(host.kmer_distance(shared), G)
+        host.write_tree_files(qry, gnames, g.ctx.tree_dist(), g.ctx.tree_joins(), g.ctx.tree_root(), tag="_km_")
 
 
 def write_region(g, qry, names, flags, groups):
@@ -658,6 +694,10 @@ def manual_print(out=None):
                  "      are resampled and every branch rated by the share of replicate trees that split the genomes the same way. single",
                  "      process only. writes <in>_fr_tree_support.nwk (Newick, percentages as node labels), _fr_tree_support.tsv,",
                  "      _fr_tree_boot.npz and, with -A 1, <in>_fr_vartree_support.nwk, _fr_vartree_support.tsv",
+                 "  -K: with -g, colour the de bruijn graph: the genomes that hold every k-mer, hence the exact k-mer spectrum, the k-mers",
+                 "      every pair of genomes shares and, with -p, the k-mer pan and core growth; no clustering is involved. 0 (off) or 1;",
+                 "      single process only, not with -D. writes <in>_km_spectrum.tsv, _km_genomes.tsv, _km_shared.tsv, _km_jaccard.tsv,",
+                 "      _km_compare.npz, with -p _km_curve.tsv and, with -T 1, _km_dist.tsv, _km_tree.nwk, _km_tree.tsv, _km_tree.npz",
                  "  -D: the reduced de bruijn graph", "  -R: break point of reduced de bruijn graph",
                  "  -v: with -g, the variable sites: pairs of regions joined in two or more ways, directly or through one region.",
                  "      0 (off) or 1; single process only. writes <in>_fr_sites.tsv, _fr_sites_genomes.tsv, _fr_sites.npz",
@@ -687,7 +727,7 @@ def parse_args(argv):
     """:1983-1997 — same flag handling, including `-k27` and skipped unknowns."""
     args = {"-i": "", "-k": "50", "-n": "2**63", "-r": "", "-d": "", "-R": "", "-D": "", "-c": "2", "-a": "mcl",
             "-w": "1", "-g": "", "-p": "0", "-l": "0", "-s": "0", "-I": "1.5", "-v": "0", "-b": "0",
-            "-V": "", "-A": "0", "-L": "0", "-T": "0", "-B": "0"}
+            "-V": "", "-A": "0", "-L": "0", "-T": "0", "-B": "0", "-K": "0"}
     N = len(argv)
     for i in range(1, N):
         k = argv[i]
@@ -813,6 +853,14 @@ def boot_arg(args, tree):
     return None if b and not tree else b
 
 
+def kmers_arg(args):
+    """-K's value: False (0) or True (1), or None for a value that is refused
+    - anything else, or 1 without -g, or 1 with -D (no dBG is loaded then)."""
+    if args["-K"] not in ("0", "1"):
+        return None
+    return None if args["-K"] == "1" and (not args["-g"] or args["-D"]) else args["-K"] == "1"
+
+
 def entry_point(argv, out=None, device=0):
     out = out or sys.stdout
     args = parse_args(argv)
@@ -825,7 +873,8 @@ def entry_point(argv, out=None, device=0):
     band = band_arg(args, align)
     tree = tree_arg(args)
     boot = boot_arg(args, tree)
-    bad = (tree is None or boot is None or not qry or n_orders is None or links is None or seqs is None or sites is None or bubbles is None or
+    kmers = kmers_arg(args)
+    bad = (kmers is None or tree is None or boot is None or not qry or n_orders is None or links is None or seqs is None or sites is None or bubbles is None or
            variants is None or align is None or band is None)
     clu = None if bad else cluster_args(args)
     if clu is None:
@@ -858,10 +907,15 @@ def entry_point(argv, out=None, device=0):
     chk = (lambda g: check_groups(g, Ns, grp, variants)) if grp and (grp != "record" or variants) else None
     chunk = 2 ** 33
     rc0, rc1 = (rc >> 1) == 1, (rc & 1) == 1
+    if kmers:
+        clu["kmers"] = True
+        clu["rc0"] = rc0
     if dbs or rdb:                                    # :2073-2101
         if not rdb:
             print("load dBG from disk", file=out)
             kmer_dict = load_graph(qry, kmer, dbs, device, rdbg=False, rc=rc0, on_parsed=chk)
+            # (-K walks the records a build over this input would insert)
+            kmer_dict.dbg_flags = host.plan_dbg(kmer_dict.seq_len, kmer_dict.shape, rc0, Ns, chunk)[0]
             print("# build the reduced dBG", file=out)
             rdbg_dict = dbg2rdbg(kmer_dict)
         else:
